@@ -1,18 +1,23 @@
 #!/usr/bin/env python3
 """Benchmark: batch 2-bit encode on MI355X (BASELINE.json configs[1]: 100M x 32-nt reads, 1 GPU).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
 One step = one ss_encode_fixed launch over one rank's batch of synthetic reads already resident in
 HBM (SURVEY §8(d) generator, generated on the device).  Ranks shard the read stream by contiguous
 index ranges (weak scaling, no data-path collective).  `value` = all ranks' nt / max-over-ranks
-time.  The same JSON line carries the other BASELINE configs as `extra` (C3 fused encode+hamming,
-C4 encode+decode round trip, C5 sharded counter with an RCCL all-to-all merge), the `roofline` of
-the dominant kernel (algorithmic bytes / HIP-event kernel time vs 8 TB/s) and the `cpu_baseline`
-(the reference's CPU algorithms restated in oracle/cpu_baseline.cpp, timed on 1 host core and on all
-usable cores for C2-C5; the reference itself never runs on the GPU box).
+time.  A plain run does only that: set up, W warmup steps, K timed steps, one JSON line with the
+`roofline` of the dominant kernel (algorithmic bytes / HIP-event kernel time vs 8 TB/s).
+`--dump-outputs DIR` also writes what the last timed step computed (dump_encode_outputs).
+
+With `--full` the same JSON line also carries the other BASELINE configs as `extra` (C3 fused
+encode+hamming, C4 encode+decode round trip, C5 sharded counter with an RCCL all-to-all merge, and
+the F / C1 / a18 lines), the `cpu_baseline` (the reference's CPU algorithms restated in
+oracle/cpu_baseline.cpp, timed on 1 host core and on all usable cores for C2-C5; the benchmark
+never runs the reference itself), and the C2 batch is compared with the generator's known answer
+(every extra keeps its own parity check).  `--no-extras` / `--no-cpu-baseline` trim a `--full` run.
 """
 from __future__ import annotations
 
@@ -169,7 +174,41 @@ def load_traffic(workload: str, reads: int):
 
 
 # ------------------------------------------------------------------------------------------------
-def bench_encode(B, lib, dev, rank, world, n, L, steps, warmup, seed=1):
+DUMP_ROWS = 1 << 20    # rows of the packed-word output kept by --dump-outputs (a seeded sample beyond that)
+DUMP_FOLD = 1 << 16    # rows per checksum block: 2^16 sums of 32-bit halves stay below 2^48, exact in float64
+
+
+def dump_encode_outputs(dump_dir, words, fb, rank, seed=0x5EED):
+    """--dump-outputs: what the last timed ss_encode_fixed step handed its caller, as float64 .npy
+    files (a packed word is 64 bits, so it is written as its low and high 32-bit halves, each exact
+    in float64; word = hi * 2^32 + lo):
+      words_rows     the read indices (within this rank's batch) of the rows kept: all of them up to
+                     DUMP_ROWS, else a sorted sample drawn once from a fixed seed
+      words_lo/_hi   [rows, words per read] halves of those rows' packed words
+      words_sum_lo/_hi  [blocks, words per read] sums of the halves over every DUMP_FOLD consecutive
+                     reads of the whole batch (every output word counts in one of them)
+      first_bad      [1] the first-invalid-read flag (-1: every read valid)
+    ~25 MB at the default batch.  Ranks beyond the first add _rank<r> to the names."""
+    os.makedirs(dump_dir, exist_ok=True)
+    n, wpr = words.shape
+    if n <= DUMP_ROWS:
+        rows = np.arange(n, dtype=np.int64)
+    else:
+        rows = np.sort(np.random.default_rng(seed).choice(n, DUMP_ROWS, replace=False)).astype(np.int64)
+    m32 = 0xFFFFFFFF
+    lo, hi = words & m32, (words >> 32) & m32
+    pad = (-n) % DUMP_FOLD
+    out = {"words_rows": rows, "first_bad": fb.cpu().numpy().reshape(-1)}
+    for name, half in (("lo", lo), ("hi", hi)):
+        out["words_" + name] = half[torch.from_numpy(rows).to(words.device)].cpu().numpy()
+        h = torch.nn.functional.pad(half, (0, 0, 0, pad)) if pad else half
+        out["words_sum_" + name] = h.view(-1, DUMP_FOLD, wpr).sum(1).cpu().numpy()
+    sfx = f"_rank{rank}" if rank else ""
+    for name, a in out.items():
+        np.save(os.path.join(dump_dir, f"{name}{sfx}.npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
+def bench_encode(B, lib, dev, rank, world, n, L, steps, warmup, seed=1, verify=True, dump_dir=None):
     i0 = rank * n
     ascii = B.synth_reads(n, L, seed=seed, i0=i0, device=dev)
     wpr = B.wpr_for(L)
@@ -184,9 +223,12 @@ def bench_encode(B, lib, dev, rank, world, n, L, steps, warmup, seed=1):
             raise RuntimeError(lib.ss_last_error_string())
 
     el, timer = timed_loop(step, steps, warmup, world)
+    if dump_dir is not None:
+        dump_encode_outputs(dump_dir, words, fb, rank)
     if int(fb.item()) != -1:
         raise SystemExit("PARITY FAILURE: synthetic batch flagged an invalid base")
-    check_known_answer(words, seed, i0, L, n)
+    if verify:
+        check_known_answer(words, seed, i0, L, n)
     del ascii, words
     # every step is exactly one encode launch (the first-bad reset is a 8-byte memset node)
     return el, timer.region_ms / steps
@@ -825,8 +867,14 @@ def main():
     # ~20 back-to-back launches run ~3% slower); 50 warmup launches of the 0.6-ms kernel ~= 30 ms
     ap.add_argument("--warmup", type=int, default=50)
     ap.add_argument("--reads-per-gpu", type=int, default=100_000_000, help="reads per GPU (C2, C3; C4 uses half)")
-    ap.add_argument("--no-extras", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="beyond the headline: the `extra` configs (C3-C5, F1-F4, C1, a18) with their parity "
+                         "checks, the C2 known-answer check and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float64; see "
+                         "dump_encode_outputs)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: leave out `extra`")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out `cpu_baseline`")
     ap.add_argument("--cpu-seconds", type=float, default=2.0, help="timed seconds per CPU-baseline leg (8 legs)")
     ap.add_argument("--dist-backend", default=os.environ.get("SHORTSEQ_DIST_BACKEND", "nccl"),
                     help="nccl (= RCCL over xGMI, default) or gloo (rehearsal: several ranks on one GPU)")
@@ -866,7 +914,8 @@ def main():
 
     L, n = 32, args.reads_per_gpu
     log(f"rank {rank}/{world}: C2 encode {n} x {L} nt")
-    el, kern_ms = bench_encode(B, lib, dev, rank, world, n, L, args.steps, args.warmup)
+    el, kern_ms = bench_encode(B, lib, dev, rank, world, n, L, args.steps, args.warmup, verify=args.full,
+                               dump_dir=args.dump_outputs)
     ms_step = el / args.steps * 1e3
     total_nt = n * L * world
     value = total_nt / (el / args.steps)
@@ -888,7 +937,7 @@ def main():
     log(f"C2: {value / 1e12:.3f} T nt/s, kernel {kern_ms:.3f} ms, {achieved:.0f} GB/s")
 
     fq_path, fq_n = None, 0
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         extra = {}
         L3, n3 = 96, args.reads_per_gpu
         log(f"C3 fused encode+hamming {n3} x {L3}")
@@ -1039,7 +1088,7 @@ def main():
         result["extra"] = extra
 
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             log("cpu baseline ...")
             result["cpu_baseline"] = cpu_baseline(args.cpu_seconds)
         else:

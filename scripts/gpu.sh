@@ -108,7 +108,7 @@ pmc)
 full)
   S=scripts/gpu_step.sh
   $S 700 pytest_gpu_$TAG python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout-method thread || exit 1
-  $S 400 bench_$TAG python bench.py --steps 20 --warmup 5 || exit 1
+  $S 400 bench_$TAG python bench.py --steps 20 --warmup 5 --full || exit 1
   python - "$TAG" <<'PY'
 import json, sys
 tag = sys.argv[1]
@@ -121,13 +121,13 @@ profall)
   S=scripts/gpu_step.sh
   P=gpurun_out/prof_$TAG
   mkdir -p $P
-  $S 300 bench_$TAG python bench.py --steps 20 --warmup 5 || exit 1
+  $S 300 bench_$TAG python bench.py --steps 20 --warmup 5 --full || exit 1
   $S 300 rocprof_stats rocprofv3 --kernel-trace --stats -d $P/trace -o run --output-format csv -- python3 bench.py --steps 20 --warmup 5 --no-extras --no-cpu-baseline || exit 1
   $S 300 rocprof_fetch rocprofv3 --pmc FETCH_SIZE -d $P/fetch -o run --output-format csv -- python3 bench.py --steps 5 --warmup 2 --no-extras --no-cpu-baseline || exit 1
   $S 300 rocprof_write rocprofv3 --pmc WRITE_SIZE -d $P/write -o run --output-format csv -- python3 bench.py --steps 5 --warmup 2 --no-extras --no-cpu-baseline || exit 1
-  $S 300 rocprof_all rocprofv3 --kernel-trace --stats -d $P/all/trace -o run --output-format csv -- python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline || exit 1
-  $S 300 rocprof_all_fetch rocprofv3 --pmc FETCH_SIZE -d $P/all/fetch -o run --output-format csv -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline || exit 1
-  $S 300 rocprof_all_write rocprofv3 --pmc WRITE_SIZE -d $P/all/write -o run --output-format csv -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline || exit 1
+  $S 300 rocprof_all rocprofv3 --kernel-trace --stats -d $P/all/trace -o run --output-format csv -- python3 bench.py --steps 10 --warmup 3 --full --no-cpu-baseline || exit 1
+  $S 300 rocprof_all_fetch rocprofv3 --pmc FETCH_SIZE -d $P/all/fetch -o run --output-format csv -- python3 bench.py --steps 3 --warmup 1 --full --no-cpu-baseline || exit 1
+  $S 300 rocprof_all_write rocprofv3 --pmc WRITE_SIZE -d $P/all/write -o run --output-format csv -- python3 bench.py --steps 3 --warmup 1 --full --no-cpu-baseline || exit 1
   echo ALLDONE ;;
 *)
   echo "unknown mode $mode"; exit 2 ;;

@@ -28,6 +28,20 @@ def test_bench_starts_ranks_without_launcher():
     assert rec["value"] is None and "dry run" in rec["data"]
 
 
+def test_bench_dry_run_takes_full_and_dump_outputs(tmp_path):
+    """The plumbing accepts the options of a real run (`--full`, `--dump-outputs DIR`) and its line
+    carries `ms_per_step`; with no GPU work there is nothing to dump."""
+    p = _run(["--gpus", "1", "--steps", "4", "--warmup", "2", "--dry-run", "--full",
+              "--dump-outputs", str(tmp_path / "d")])
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, p.stdout
+    rec = json.loads(lines[0])
+    assert rec["steps"] == 4 and rec["warmup"] == 2 and rec["ms_per_step"] >= 0
+    assert rec["unit"] == "nt/s" and rec["higher_is_better"] is True and rec["dtype"] == "u8"
+    assert not (tmp_path / "d").exists()
+
+
 def test_bench_refuses_mismatched_world():
     p = _run(["--gpus", "4", "--steps", "1", "--warmup", "0", "--dry-run"],
              {"WORLD_SIZE": "1", "RANK": "0", "LOCAL_RANK": "0"})

@@ -181,7 +181,7 @@ def test_bench_two_ranks_rehearsal():
     env = dict(os.environ, PYTHONUNBUFFERED="1")
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                         "--master-addr", "127.0.0.1", "--master-port", str(port), "bench.py", "--gpus", "2",
-                        "--steps", "3", "--warmup", "1", "--dist-backend", "gloo", "--same-device"],
+                        "--steps", "3", "--warmup", "1", "--dist-backend", "gloo", "--same-device", "--full"],
                        cwd=REPO, env=env, capture_output=True, text=True, timeout=540)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
