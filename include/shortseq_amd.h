@@ -172,6 +172,9 @@ int ss_hamming_all_pairs_ex(const uint64_t* d_words, uint64_t n, uint32_t L, uin
  * packed words) (short_seq_64.pyx:41-44; short_seq_192.pyx:35-41), count += 1, first-occurrence
  * index kept so the host can rebuild dict insertion order.  Open-addressing table in HBM, one per
  * handle; all keys of one handle share one length L <= 1024 (the length is part of the key).
+ * The packed word ~0 ("G" * 32) equals the table's EMPTY mark and is counted in a slot of its own,
+ * whose key field says nothing: that key is present iff its count (the slot's u32 part plus its entry
+ * of the u64 array below) is nonzero.
  * L <= 32: the slot key is the packed word.  L > 32: W = ceil(L/32) words per key, kept beside the
  * slots; the slot holds a 64-bit fingerprint of the words and equality is decided on the words.
  * A slot is 16 B (key u64, count u32, first index u32): global read indices of one handle stay below
@@ -352,7 +355,9 @@ int ss_counter_merge_runs(ss_counter* c, const uint64_t* d_keys, const uint64_t*
  *   sentinel key ~0 last in its owner's segment; written to d_rec (16-byte aligned, cap records);
  *   d_part_counts[n_parts] (0 for skip_part).  One pass over the table after a partitioned insert
  *   (its aggregate keeps the per-region occupancy), two otherwise.  A count or first - first_base
- *   that does not fit 32 bits, or more than cap records, raises the overflow word (bits 4 / 2).
+ *   that does not fit 32 bits, or more than cap records, raises the overflow word (values 4 / 2,
+ *   i.e. bits 2 / 1 of ss_counter_overflow); a record's count is the entry's whole u64 count, so one
+ *   that fits is never flagged, however it is split between the slot and the u64 array.
  * ss_counter_merge_packed: as ss_counter_merge_runs for packed runs; run r's first indices are
  *   relative to d_run_first_base[r] (the source rank's first_base). */
 int ss_counter_pack_ranges(ss_counter* c, uint32_t n_parts, int32_t skip_part, uint64_t first_base, void* d_rec,

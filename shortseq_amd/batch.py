@@ -873,7 +873,9 @@ class GpuCounter:
     def pack_ranges(self, n_parts: int, skip: int = -1, first_base: int = 0, cap: Optional[int] = None):
         """Region-range parts as packed 16-B records (ss_counter_pack_ranges) -> (rec int64 [cap, 2],
         part_counts int64 [n_parts]) on the device; rec[:, 0] = key, rec[:, 1] = count | (first -
-        first_base) << 32; part `skip` is left out (count 0).  Raises if a record field overflowed."""
+        first_base) << 32; part `skip` is left out (count 0).  Does not raise: a count or first -
+        first_base that does not fit its 32-bit field sets value 4 in overflow_word(), more than cap
+        records value 2; the caller checks the word (ShardedCounter sends it along the exchange)."""
         cap = self.capacity + 1 if cap is None else cap
         d = self.device
         rec = torch.empty((cap, 2), dtype=torch.int64, device=d)

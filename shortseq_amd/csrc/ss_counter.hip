@@ -11,7 +11,10 @@
 // refused up front when base_index + n says so.
 // One slot = one dwordx4: the probe load, the count atomic and the first-index check touch the same
 // 16 B, and a fresh slice is written back as one dwordx4 store per slot.
-// The packed word ~0 ("G" * 32) collides with EMPTY and lives in the sentinel slot C.
+// The packed word ~0 ("G" * 32) collides with EMPTY and lives in the sentinel slot C.  That slot's key
+// field says nothing: the sentinel is present iff its count is nonzero, the count being the slot's
+// u32 plus the slot's entry of the u64 count array while that array is live (a merge can carry the
+// u32 part to exactly 0; slot_used tests both).
 // Every key of one handle has the same length L <= 32 (the host groups a mixed batch by length, so
 // the dict key (length, packed) of short_seq_64.pyx:41-44 is (handle, word) here).
 //
@@ -102,7 +105,9 @@ struct ss_counter {
     // zeroed when it goes live) holds the rest.  Inserts add at most one per read, so before the reads
     // inserted since the last spill could pass spill_at, every slot's count moves into wide
     // (k_spill_wide) and the slot restarts at 0 (the sentinel keeps 1); merges carry into wide as they
-    // add.  Nothing reads wide while it is not live (tbl_of passes null), so the C5 insert is unchanged.
+    // add, which can leave the sentinel's u32 at 0 with its count in wide: it is present iff either is
+    // nonzero (slot_used).  Nothing reads wide while it is not live (tbl_of passes null), so the C5
+    // insert is unchanged.
     uint64_t* wide = nullptr;              // [cap + 1]
     bool wide_live = false;
     uint64_t since = 0;                    // reads inserted since the last reset / spill (kSinceUnknown after a merge)
@@ -297,7 +302,8 @@ __device__ __forceinline__ bool slot_used(const Tbl& t, uint64_t s, uint64_t& ke
         return key != kEmpty;
     }
     key = kEmpty;
-    return sl.ncount != 0xFFFFFFFFu;   // sentinel slot: used iff its count is nonzero
+    // sentinel slot: used iff its count is nonzero -- the u32 part or, after a carry, the u64 part
+    return sl.ncount != 0xFFFFFFFFu || (t.wide && t.wide[s] != 0);
 }
 
 __global__ __launch_bounds__(kThreads) void k_size(Tbl t, unsigned long long* out) {
@@ -2172,11 +2178,12 @@ __global__ __launch_bounds__(kPackT) void k_region_pack(Tbl t, uint32_t R, uint3
             const bool used = !(a[u].x == 0xFFFFFFFFu && a[u].y == 0xFFFFFFFFu);
             const unsigned long long pos = wave_reserve(used, 0u, &cursor);
             if (!used) continue;
-            const uint32_t c = ~a[u].z;
-            // the 16-B record carries a u32 count: a count with a high part (wide) cannot cross
-            if (a[u].w < first_base || (t.wide && t.wide[base + i0 + u * kPackT + threadIdx.x])) atomicOr(flags, kOvfField);
+            // the 16-B record carries a u32 count: the slot's u32 plus its u64 part must fit it
+            const unsigned long long c =
+                (unsigned long long)(uint32_t)~a[u].z + (t.wide ? t.wide[base + i0 + u * kPackT + threadIdx.x] : 0ull);
+            if (a[u].w < first_base || (c >> 32)) atomicOr(flags, kOvfField);
             if (pos < cap)
-                rec[pos] = make_uint4(a[u].x, a[u].y, c, (uint32_t)(a[u].w - first_base));
+                rec[pos] = make_uint4(a[u].x, a[u].y, (uint32_t)c, (uint32_t)(a[u].w - first_base));
             else
                 atomicOr(flags, kOvfExtract);
         }
@@ -2574,8 +2581,9 @@ int wide_on(ss_counter* c, hipStream_t s) {
     return ss_check(hipMemsetAsync(c->wide, 0, (c->cap + 1) * sizeof(uint64_t), s), "counter wide counts reset");
 }
 
-// Every slot's count into wide (the sentinel slot, present iff its count is nonzero, keeps 1): the
-// slots restart below 2 and take another spill_at reads before the next spill.
+// Every slot's count into wide (the sentinel slot keeps 1 of a nonzero u32 part; one a merge carried to
+// 0 stays 0, its count is in wide already): the slots restart below 2 and take another spill_at reads
+// before the next spill.
 __global__ __launch_bounds__(256) void k_spill_wide(Tbl t) {
     for (uint64_t s = (uint64_t)blockIdx.x * 256 + threadIdx.x; s <= t.mask + 1; s += (uint64_t)gridDim.x * 256) {
         const Slot sl = t.slots[s];

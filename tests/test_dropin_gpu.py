@@ -50,12 +50,9 @@ def test_counter_gpu_equals_host_mixed(gpu):
     assert dev[sq.pack("G" * 32)] == host[sq.pack("G" * 32)]
 
 
-def test_counter_gpu_short_group(gpu):
-    """Lengths 1..31 share one table (each key = the packed word with a length marker above it and
-    above its table-path carry bit): a read whose last byte is aliased (\\x01 \\x03 \\x07 \\x14, whose
-    carry lands on bit 2L) stays apart from the read with an 'A' there and from the read one base
-    longer; ragged and dense (one-length) batches; the first rejected read is the first in input
-    order across lengths."""
+def _short_group_reads():
+    """Every length 1..31, each with last bytes \\x01 \\x03 \\x07 \\x14 A, plus the read one base longer;
+    60 000 draws -> (rng, pool, reads)."""
     rng = random.Random(41)
     pool = []
     for L in range(1, 32):
@@ -65,6 +62,16 @@ def test_counter_gpu_short_group(gpu):
             pool += [s[:-1] + a for a in (b"\x01", b"\x03", b"\x07", b"\x14", b"A")]
             pool.append(s + b"A")
     reads = [rng.choice(pool) for _ in range(60_000)]
+    return rng, pool, reads
+
+
+def test_counter_gpu_short_group(gpu):
+    """Lengths 1..31 share one table (each key = the packed word with a length marker above it and
+    above its table-path carry bit): a read whose last byte is aliased (\\x01 \\x03 \\x07 \\x14, whose
+    carry lands on bit 2L) stays apart from the read with an 'A' there and from the read one base
+    longer; ragged and dense (one-length) batches; the first rejected read is the first in input
+    order across lengths."""
+    rng, pool, reads = _short_group_reads()
     host = ShortSeqCounter(reads, device="host")
     assert _items(ShortSeqCounter(reads, device="cuda")) == _items(host)
     for L in (1, 7, 20, 31):
@@ -79,6 +86,34 @@ def test_counter_gpu_short_group(gpu):
     with pytest.raises(Exception) as ei_d:
         ShortSeqCounter(bad, device="cuda")
     assert str(ei_d.value) == str(ei_h.value) == "Unsupported base character: X"
+
+
+def test_counter_gpu_short_group_oracle(gpu, oracle):
+    """The same pool against the oracle, not the product's own host path: the reads as a ragged device
+    batch through the drop-in engine (DeviceIngest.count, two calls: global read indices continue);
+    results() lengths, counts and words, in first-occurrence order, equal oracle.count(reads)."""
+    import numpy as np
+    import torch
+    import shortseq_amd.batch as B
+    _rng, _pool, reads = _short_group_reads()
+    exp = oracle.count(reads)
+    lens_h = np.array([len(r) for r in reads], dtype=np.int32)
+    offs_h = np.zeros(len(reads), dtype=np.int64)
+    offs_h[1:] = np.cumsum(lens_h[:-1], dtype=np.int64)
+    blob = torch.frombuffer(bytearray(b"".join(reads) + b"A" * 16), dtype=torch.uint8).to(gpu)
+    offs, lens = torch.from_numpy(offs_h).to(gpu), torch.from_numpy(lens_h).to(gpu)
+    h = len(reads) // 2
+    eng = B.DeviceIngest(gpu)
+    try:
+        eng.count(blob, offs[:h], lens[:h])
+        eng.count(blob, offs[h:], lens[h:])
+        gl, gc, gw = eng.results()
+    finally:
+        eng.close()
+    assert gl.tolist() == [L for (_w, L, _c, _f) in exp]
+    assert gc.tolist() == [c for (_w, _L, c, _f) in exp]
+    assert gw.tolist() == [w[0] for (w, _L, _c, _f) in exp]      # one word per row: every length <= 32
+    assert sum(gc.tolist()) == len(reads)
 
 
 def test_counter_gpu_errors_first_bad(gpu):
