@@ -12,8 +12,8 @@
  *     safe to capture in a hipGraph.  They return SS_OK or a launch/argument error immediately.
  *     Exceptions, each documented at its declaration: the counter and ingest handles (their own
  *     workspaces; the ingest calls are synchronous), and ss_hamming_all_pairs / _ex when they take
- *     the pigeonhole form (a per-device scratch buffer cached across calls; AUTO reads its candidate
- *     totals back with one stream sync).  SS_ALLPAIRS_TILES keeps the plain contract.
+ *     the pigeonhole / bucketed form (a per-device scratch buffer cached across calls; AUTO reads its
+ *     candidate totals back with one stream sync).  SS_ALLPAIRS_TILES keeps the plain contract.
  *   - Validation mirrors util.pxd:98-99 (bloom filter 0xFFFFFFFFFFEFFF75, util.pyx:75).  A kernel
  *     that meets an invalid byte writes the index of the FIRST invalid read (input order) into
  *     *d_first_bad (atomicMin; the entry point resets it to UINT64_MAX first).  The caller re-scans
@@ -42,7 +42,7 @@ enum ss_status {
     SS_ETOO_LONG = 2,       /* "Sequences longer than 1024 bases are not supported." (short_seq.pyx:74) */
     SS_EARG = -1,           /* bad argument (NULL pointer, L out of range, wpr too small, misalignment) */
     SS_EHIP = -2,           /* HIP runtime error; see ss_last_error_string() */
-    SS_ENOMEM = -3,         /* device allocation failed (counter handles, forced pigeonhole all-pairs) */
+    SS_ENOMEM = -3,         /* device allocation failed (counter handles, forced all-pairs scratch) */
     SS_EFULL = -4           /* counter table full */
 };
 
@@ -157,12 +157,25 @@ int ss_hamming_all_pairs(const uint64_t* d_words, uint64_t n, uint32_t L, uint32
  *   segment are checked (bucketed per segment on the device; a segment past 11 nt by a hash).
  *   Blocks the calling thread once on the stream (the candidate totals are read back) only in AUTO;
  *   forced, it queues everything.  Its scratch lives on the device that holds d_words.
+ * BUCKETED (any L <= 1024, any wpr >= W, max_dist <= 31; more is SS_EARG): the same segment rule past
+ *   PIGEONHOLE's range.  L <= 128 with max_dist < 16 runs PIGEONHOLE itself; everything else (W >= 5
+ *   words, or max_dist 16 .. 31 at any W) runs the long form: rows are not copied into bucket order
+ *   (only read indices are; candidate rows are read from d_words, a group of 4 .. 32 lanes per row),
+ *   so its scratch does not grow with W.  Scratch per call, G = max_dist + 1 segments and
+ *   b = clamp(ceil(log2 n), 10, 22) bucket bits: G * (4 << b) B of histogram, 12 B per 4096 buckets,
+ *   and G * n * 8 B of indices (PIGEONHOLE adds G * n * 8 W B of copied rows).  Forced, a scratch
+ *   that cannot be allocated is SS_ENOMEM; in AUTO the tiles run instead.  Padding words (wpr > W)
+ *   are never read.
  * AUTO: PIGEONHOLE when L <= 128, segments >= 3 nt, n >= 32768 and the bucket histogram shows fewer
- *   than 1/16 of all pairs as candidates; TILES otherwise.  A stream under hipGraph capture always
- *   gets TILES in AUTO (no allocation, no host read-back: the call stays capturable). */
+ *   than 1/16 of all pairs as candidates; the long form of BUCKETED when L > 128, max_dist <= 31,
+ *   n >= 32768 and the histogram shows fewer than 1/32 of all pairs (kPiglRatio, measured apart from
+ *   the 1/16: the other side is the slower bit-plane tiles and a candidate costs a gathered row);
+ *   TILES otherwise.  A stream under hipGraph capture always gets TILES in AUTO (no allocation, no
+ *   host read-back: the call stays capturable). */
 #define SS_ALLPAIRS_AUTO 0u
 #define SS_ALLPAIRS_TILES 1u
 #define SS_ALLPAIRS_PIGEONHOLE 2u
+#define SS_ALLPAIRS_BUCKETED 3u
 int ss_hamming_all_pairs_ex(const uint64_t* d_words, uint64_t n, uint32_t L, uint32_t wpr, uint32_t max_dist,
                             uint32_t* d_counts, uint32_t* d_pairs, uint64_t max_pairs, uint64_t* d_npairs,
                             uint32_t method, void* stream);

@@ -610,7 +610,7 @@ def slice_var(words: torch.Tensor, starts: torch.Tensor, lens: torch.Tensor, *,
     return out
 
 
-ALL_PAIRS_METHODS = {"auto": 0, "tiles": 1, "pigeonhole": 2}
+ALL_PAIRS_METHODS = {"auto": 0, "tiles": 1, "pigeonhole": 2, "bucketed": 3}
 
 
 def hamming_all_pairs(words: torch.Tensor, L: int, max_dist: int, *, counts: bool = True,
@@ -618,7 +618,9 @@ def hamming_all_pairs(words: torch.Tensor, L: int, max_dist: int, *, counts: boo
     """Unordered pairs (i < j) of a packed batch within `max_dist` (the reference __xor__ distance)
     -> (neighbour counts int32 [n] or None, pairs int32 [m, 2] or None, total pairs).  Pairs are
     returned sorted; at most max_pairs are kept (0: count only).  method: "tiles" checks every pair,
-    "pigeonhole" (L <= 128) only pairs sharing one of max_dist + 1 segments, "auto" picks
+    "pigeonhole" (L <= 128, max_dist < 16) only pairs sharing one of max_dist + 1 segments,
+    "bucketed" the same rule for any L <= 1024 and max_dist <= 31 (past pigeonhole's range the rows
+    stay where they are and are read through bucket-ordered indices), "auto" picks
     (ss_hamming_all_pairs_ex); the results are the same."""
     _require_cuda(words, "words")
     n, wpr = words.shape

@@ -466,7 +466,8 @@ __device__ __forceinline__ T block_sum256(T v, T* red) {
 // per tile of 4096 buckets: number of reads and candidate pairs; the grid's last block to finish
 // then scans every segment's tile sums (<= 1024 tiles: 4 per thread) into tile bases and the
 // segment's candidate total -- no separate scan launch
-__global__ __launch_bounds__(256) void k_pig_tile(PigArgs a) {
+template <typename A>   // PigArgs or PiglArgs: only the histogram fields are read
+__global__ __launch_bounds__(256) void k_pig_tile(A a) {
     const uint32_t g = blockIdx.y, t0 = blockIdx.x * kPigTile, nbk = 1u << a.nb[g];
     __shared__ uint32_t r32[4];
     __shared__ uint64_t r64[4];
@@ -530,7 +531,8 @@ __global__ __launch_bounds__(256) void k_pig_tile(PigArgs a) {
 }
 
 // bucket starts: each thread owns 16 consecutive buckets of the tile
-__global__ __launch_bounds__(256) void k_pig_apply(PigArgs a) {
+template <typename A>
+__global__ __launch_bounds__(256) void k_pig_apply(A a) {
     const uint32_t g = blockIdx.y, t0 = blockIdx.x * kPigTile, nbk = 1u << a.nb[g];
     if (t0 >= nbk) return;
     uint32_t* h = a.hist + ((uint64_t)g << a.nbmax) + t0;
@@ -587,7 +589,8 @@ __device__ __forceinline__ void lds_wave_sync() {
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
-__device__ __forceinline__ void hits_flush(const PigArgs& a, WaveHits& wh) {
+template <typename A>
+__device__ __forceinline__ void hits_flush(const A& a, WaveHits& wh) {
     if (!wh.fill) return;
     lds_wave_sync();
     const uint32_t lane = threadIdx.x & 63u;
@@ -605,7 +608,8 @@ __device__ __forceinline__ void hits_flush(const PigArgs& a, WaveHits& wh) {
     lds_wave_sync();
     wh.fill = 0;
 }
-__device__ __forceinline__ void hits_add(const PigArgs& a, WaveHits& wh, bool hit, uint64_t mask, uint32_t i, uint32_t j) {
+template <typename A>
+__device__ __forceinline__ void hits_add(const A& a, WaveHits& wh, bool hit, uint64_t mask, uint32_t i, uint32_t j) {
     const uint32_t c = (uint32_t)__popcll(mask);
     if (!a.pairs) {
         wh.nh += c;
@@ -891,6 +895,66 @@ struct PigScratch {
     uint64_t* h_cand = nullptr;   // pinned: the candidate totals read back
 };
 PigScratch g_pig[64];
+constexpr int kPiglMaxG = 32;             // the long form's segment bound (k_pigl_*, below)
+
+// A call's hold on the scratch of the device that holds `words` (the kernels run there, on the
+// caller's stream), not of whichever device is current: that device made current and the
+// scratch locked until the hold goes.  acquire() leaves ps->p with >= need bytes, ordered after the
+// previous call's kernels; *have = false (rc 0) when the memory could not be had and the call was
+// not forced: the outputs are then zeroed for the tiled form, which needs no scratch.
+struct PigHold {
+    int prev = 0, now = 0;
+    PigScratch* ps = nullptr;
+    std::unique_lock<std::mutex> lock;
+    ~PigHold() {
+        if (lock.owns_lock()) lock.unlock();
+        if (prev != now) (void)hipSetDevice(prev);
+    }
+    int acquire(const void* words, size_t need, bool forced, hipStream_t s, unsigned long long* npairs,
+                uint32_t* counts, uint64_t n, bool* have) {
+        *have = false;
+        int rc = ss_check(hipGetDevice(&prev), "hipGetDevice");
+        now = prev;
+        if (rc) return rc;
+        hipPointerAttribute_t pa{};
+        rc = ss_check(hipPointerGetAttributes(&pa, words), "all-pairs: words pointer attributes");
+        if (rc) return rc;
+        if (pa.device < 0 || pa.device >= 64) return ss_fail(SS_EARG, "all-pairs: device index past 63");
+        if (pa.device != prev) {
+            rc = ss_check(hipSetDevice(pa.device), "all-pairs: hipSetDevice");
+            if (rc) return rc;
+            now = pa.device;
+        }
+        ps = &g_pig[now];
+        lock = std::unique_lock<std::mutex>(ps->mu);
+        if (!ps->done) rc = ss_check(hipEventCreateWithFlags(&ps->done, hipEventDisableTiming), "pig event");
+        if (!rc && !ps->h_cand)
+            rc = ss_check(hipHostMalloc((void**)&ps->h_cand, kPiglMaxG * 8, hipHostMallocDefault), "pinned totals");
+        if (!rc && ps->bytes < need) {
+            if (ps->p) {
+                rc = ss_check(hipEventSynchronize(ps->done), "pig scratch idle");
+                if (!rc) rc = ss_check(hipFree(ps->p), "pig scratch free");
+                ps->p = nullptr;
+                ps->bytes = 0;
+            }
+            const size_t want = need + need / 4;
+            if (!rc && hipMalloc(&ps->p, want) != hipSuccess) {
+                (void)hipGetLastError();
+                ps->p = nullptr;
+                if (forced) return ss_fail(SS_ENOMEM, "pigeonhole all-pairs scratch: out of device memory");
+                // auto: the tiled form gets the outputs zeroed as the entry skipped that
+                rc = ss_check(hipMemsetAsync(npairs, 0, sizeof(uint64_t), s), "npairs reset");
+                if (!rc && counts) rc = ss_check(hipMemsetAsync(counts, 0, n * sizeof(uint32_t), s), "counts reset");
+                return rc;
+            }
+            if (!rc) ps->bytes = want;
+        } else if (!rc) {
+            rc = ss_check(hipStreamWaitEvent(s, ps->done, 0), "pig scratch wait");
+        }
+        if (!rc) *have = true;
+        return rc;
+    }
+};
 
 // returns 0 with *done = false when the auto choice hands the batch to the tiled form
 int pig_all_pairs(const AllPairsArgs& b, uint32_t L, uint32_t P, bool forced, hipStream_t s, bool* done) {
@@ -925,54 +989,13 @@ int pig_all_pairs(const AllPairsArgs& b, uint32_t L, uint32_t P, bool forced, hi
         pos += len;
     }
     a.seg[a.G] = P;
-    // the scratch, its event and the pinned totals belong to the device that holds the words (the
-    // kernels run there, on the caller's stream), not to whichever device is current
-    int cur = 0, dev = 0;
-    int rc = ss_check(hipGetDevice(&cur), "hipGetDevice");
-    if (rc) return rc;
-    hipPointerAttribute_t pa{};
-    rc = ss_check(hipPointerGetAttributes(&pa, b.words), "all-pairs: words pointer attributes");
-    if (rc) return rc;
-    dev = pa.device;
-    if (dev < 0 || dev >= 64) return ss_fail(SS_EARG, "all-pairs: device index past 63");
-    struct DevGuard {
-        int prev, now;
-        ~DevGuard() {
-            if (prev != now) (void)hipSetDevice(prev);
-        }
-    } guard{cur, dev};
-    if (dev != cur) {
-        rc = ss_check(hipSetDevice(dev), "all-pairs: hipSetDevice");
-        if (rc) return rc;
-    }
-    PigScratch& ps = g_pig[dev];
-    std::lock_guard<std::mutex> lock(ps.mu);
     const size_t hist_n = (size_t)a.G << a.nbmax, tiles_n = (size_t)a.G * a.maxtiles;
     const size_t need = tiles_n * 8 + a.G * 8 + (hist_n + 2) * 4 + tiles_n * 4 + 64 + (size_t)a.G * a.n * (8 * a.W + 8);
-    if (!ps.done) rc = ss_check(hipEventCreateWithFlags(&ps.done, hipEventDisableTiming), "pig event");
-    if (!rc && !ps.h_cand) rc = ss_check(hipHostMalloc((void**)&ps.h_cand, kPigMaxG * 8, hipHostMallocDefault), "pinned totals");
-    if (!rc && ps.bytes < need) {
-        if (ps.p) {
-            rc = ss_check(hipEventSynchronize(ps.done), "pig scratch idle");
-            if (!rc) rc = ss_check(hipFree(ps.p), "pig scratch free");
-            ps.p = nullptr;
-            ps.bytes = 0;
-        }
-        const size_t want = need + need / 4;
-        if (!rc && hipMalloc(&ps.p, want) != hipSuccess) {
-            (void)hipGetLastError();
-            ps.p = nullptr;
-            if (forced) return ss_fail(SS_ENOMEM, "pigeonhole all-pairs scratch: out of device memory");
-            // auto: the tiled form needs no scratch; it gets the outputs zeroed as the entry skipped that
-            rc = ss_check(hipMemsetAsync(a.npairs, 0, sizeof(uint64_t), s), "npairs reset");
-            if (!rc && a.counts) rc = ss_check(hipMemsetAsync(a.counts, 0, a.n * sizeof(uint32_t), s), "counts reset");
-            return rc;
-        }
-        if (!rc) ps.bytes = want;
-    } else if (!rc) {
-        rc = ss_check(hipStreamWaitEvent(s, ps.done, 0), "pig scratch wait");
-    }
-    if (rc) return rc;
+    PigHold hold;
+    bool have = false;
+    int rc = hold.acquire(b.words, need, forced, s, a.npairs, a.counts, a.n, &have);
+    if (rc || !have) return rc;
+    PigScratch& ps = *hold.ps;
     char* q = (char*)ps.p;
     a.tile_cand = (uint64_t*)q;
     a.cand = a.tile_cand + tiles_n;
@@ -990,7 +1013,7 @@ int pig_all_pairs(const AllPairsArgs& b, uint32_t L, uint32_t P, bool forced, hi
         else if (a.W == 2) hipLaunchKernelGGL(k_pigw_hist<2>, dim3(rgrid), dim3(256), 0, s, a);
         else if (a.W == 3) hipLaunchKernelGGL(k_pigw_hist<3>, dim3(rgrid), dim3(256), 0, s, a);
         else hipLaunchKernelGGL(k_pigw_hist<4>, dim3(rgrid), dim3(256), 0, s, a);
-        hipLaunchKernelGGL(k_pig_tile, tgrid, dim3(256), 0, s, a);
+        hipLaunchKernelGGL(k_pig_tile<PigArgs>, tgrid, dim3(256), 0, s, a);
         rc = ss_check(hipGetLastError(), "k_pig_hist/tile");
     }
     bool use = forced;
@@ -1003,7 +1026,7 @@ int pig_all_pairs(const AllPairsArgs& b, uint32_t L, uint32_t P, bool forced, hi
         use = cand < a.n * (a.n - 1) / 2 / kPigRatio;
     }
     if (!rc && use) {
-        hipLaunchKernelGGL(k_pig_apply, tgrid, dim3(256), 0, s, a);
+        hipLaunchKernelGGL(k_pig_apply<PigArgs>, tgrid, dim3(256), 0, s, a);
         if (a.W == 1) hipLaunchKernelGGL(k_pig_scatter, dim3(rgrid), dim3(256), 0, s, a);
         else if (a.W == 2) hipLaunchKernelGGL(k_pigw_scatter<2>, dim3(rgrid), dim3(256), 0, s, a);
         else if (a.W == 3) hipLaunchKernelGGL(k_pigw_scatter<3>, dim3(rgrid), dim3(256), 0, s, a);
@@ -1024,6 +1047,264 @@ int pig_all_pairs(const AllPairsArgs& b, uint32_t L, uint32_t P, bool forced, hi
     return rc ? rc : r2;
 }
 
+// ------------------------------------------------------------------------------------------------
+// Long form (SS_ALLPAIRS_BUCKETED past pig_all_pairs' range: W = 5 .. 32 words, or max_dist 16 .. 31
+// at any W).  The same pigeonhole argument and segment split, for a runtime W and G <= 32.  Two
+// things differ from k_pigw_*:
+//  - no row copies: bucket order holds read indices only (sid), and candidate rows are read from
+//    `words` through them.  Scratch per call = G (4 << nbmax) B of histogram + 12 B per scan tile
+//    + G * n * 8 B (sid + rank); copied rows would add G * n * 8 W B (8 GB at n = 1M, W = G = 32).
+//  - load shape: a group of LG = 4 / 8 / 16 / 32 lanes (the power of two >= W) per entry, one 8-byte
+//    word of the row per lane, so a candidate row is one contiguous 8 W-byte piece of a wave load
+//    instead of 64 lanes in 64 rows.  8-byte pieces are aligned for every wpr (a 16-byte piece is
+//    not when wpr is odd, the 129 .. 160-nt case); lanes at word >= W load nothing and add zero, so
+//    no read goes past a row's W words (wpr may equal W).
+// k_pigl_scatter overwrites rank[g][i] with the end of read i's bucket, so the pairs kernel gets an
+// entry's run (p, end) from its index alone and never hashes.  A group walks its run kPiglStep
+// candidates per step (their indices fetched a step ahead, the rows in flight together); the wave
+// leaves the loop when no group has candidates left.  Nothing is sized by a run's length, so a
+// bucket of n entries (one repeated read) is walked correctly, in n / kPiglStep steps.
+// Measured and not kept (profiles/r7/ab_four_entries_per_group.log): four consecutive entries per
+// group, each candidate row loaded once for the four and the tile's own rows its first candidates
+// (112 VGPRs, 4 waves per SIMD): sparse buckets 0.124 -> 0.103 ms (100k x 150 nt, pool 2^16) and
+// 0.454 -> 0.358 ms (50k x 1024 nt), but buckets of ~400 reads 1.73 -> 2.16 ms and 2.52 -> 3.09 ms.
+// ------------------------------------------------------------------------------------------------
+struct PiglArgs {
+    const uint64_t* words;
+    uint64_t n;
+    uint32_t wpr, W, k, G, nbmax, maxtiles, exact, P;   // exact: bit g = segment g buckets by value
+    uint32_t nb[kPiglMaxG];
+    uint32_t seg[kPiglMaxG + 1];   // segment g = positions [seg[g], seg[g + 1]) of the row's P
+    uint32_t* hist;
+    uint32_t* tile_cnt;
+    uint64_t* tile_cand;
+    uint64_t* cand;
+    uint32_t* done;
+    uint32_t zero_out;
+    uint32_t* sid;        // G * n read indices in bucket order
+    uint32_t* rank;       // G * n: read i's rank in its bucket (k_pigl_hist), then that bucket's end (k_pigl_scatter)
+    uint32_t* counts;
+    uint32_t* pairs;
+    uint64_t max_pairs;
+    unsigned long long* npairs;
+};
+
+// bits [2 b0, 2 b0 + 64) of the row at r (b0 in positions, < 32 W); no word at or past W is read
+__device__ __forceinline__ uint64_t rowl_bits64(const uint64_t* r, uint32_t W, uint32_t b0) {
+    const uint32_t q = b0 >> 5, sh = 2u * (b0 & 31u);
+    const uint64_t lo = r[q];
+    if (!sh) return lo;
+    const uint64_t hi = q + 1u < W ? r[q + 1u] : 0ull;
+    return (lo >> sh) | (hi << (64u - sh));
+}
+// pigw_bucket for a runtime W (the same value and hash); an empty segment is bucket 0
+__device__ __forceinline__ uint32_t pigl_bucket(const PiglArgs& a, uint32_t g, const uint64_t* r) {
+    const uint32_t p0 = a.seg[g], len = a.seg[g + 1] - p0;
+    if (!len) return 0u;
+    if ((a.exact >> g) & 1u) return (uint32_t)(rowl_bits64(r, a.W, p0) & ((1ull << (2u * len)) - 1ull));
+    uint64_t h = 0x243F6A8885A308D3ull ^ len;
+    for (uint32_t b = 0; b < len; b += 32) {
+        const uint32_t m = len - b < 32u ? len - b : 32u;
+        uint64_t v = rowl_bits64(r, a.W, p0 + b);
+        if (m < 32u) v &= (1ull << (2u * m)) - 1ull;
+        h = (h ^ v) * 0x9E3779B97F4A7C15ull;
+        h ^= h >> 29;
+    }
+    return (uint32_t)(h >> (64 - a.nb[g]));
+}
+
+// a thread per read, every segment in turn (a thread per (segment, read) measured no faster at 100k x
+// 150 nt, 20 vs 20 us, and slower at 50k x 1024 nt, G = 17: hist 38 -> 43 us, scatter 27 -> 35 us)
+__global__ __launch_bounds__(256) void k_pigl_hist(PiglArgs a) {
+    if (a.zero_out && blockIdx.x == 0 && threadIdx.x == 0) *a.npairs = 0ull;
+    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < a.n; i += (uint64_t)gridDim.x * 256) {
+        if (a.zero_out && a.counts) a.counts[i] = 0u;
+        const uint64_t* r = a.words + i * a.wpr;
+        for (uint32_t g = 0; g < a.G; ++g)
+            a.rank[g * a.n + i] = atomicAdd(&a.hist[((uint64_t)g << a.nbmax) + pigl_bucket(a, g, r)], 1u);
+    }
+}
+
+__global__ __launch_bounds__(256) void k_pigl_scatter(PiglArgs a) {
+    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < a.n; i += (uint64_t)gridDim.x * 256) {
+        const uint64_t* r = a.words + i * a.wpr;
+        for (uint32_t g = 0; g < a.G; ++g) {
+            const uint32_t* start = a.hist + ((uint64_t)g << a.nbmax);
+            const uint32_t b = pigl_bucket(a, g, r), nbk = 1u << a.nb[g];
+            const uint32_t pos = start[b] + a.rank[g * a.n + i];
+            a.sid[g * a.n + pos] = (uint32_t)i;
+            a.rank[g * a.n + i] = b + 1u < nbk ? start[b + 1u] : (uint32_t)a.n;   // this read's bucket end
+        }
+    }
+}
+
+constexpr int kPiglStep = 4;
+template <int LG>   // lanes per entry, one row word each: W <= LG
+__global__ __launch_bounds__(256) void k_pigl_pairs(PiglArgs a) {
+    __shared__ uint2 pbuf[4][kPairBuf];
+    __shared__ uint32_t s_seg[kPiglMaxG + 1];
+    __shared__ unsigned long long s_hits;
+    if (threadIdx.x == 0) {
+        s_hits = 0;
+        for (uint32_t h = 0; h <= a.G; ++h) s_seg[h] = a.seg[h];   // (lanes index it per position below)
+    }
+    __syncthreads();
+    const uint32_t g = blockIdx.y, lane = threadIdx.x & 63u, l = threadIdx.x & (LG - 1u);
+    const uint64_t p = (uint64_t)blockIdx.x * (256 / LG) + threadIdx.x / LG;   // the group's entry
+    const bool valid = p < a.n, live = l < a.W;
+    const uint32_t* sid = a.sid + g * a.n;
+    const uint32_t id = valid ? sid[p] : 0u;
+    const uint64_t end = valid ? a.rank[g * a.n + id] : 0ull;
+    const uint64_t w = valid && live ? a.words[(uint64_t)id * a.wpr + l] : 0ull;
+    // this lane's word holds positions [32 l, 32 l + 32); those below P compare (the low bit of each code)
+    const uint32_t np = live && a.P > 32u * l ? min(32u, a.P - 32u * l) : 0u;
+    const uint64_t pm = np >= 32u ? 0x5555555555555555ull : 0x5555555555555555ull & ((1ull << (2u * np)) - 1ull);
+    uint32_t s0 = 0;                                   // the segment of this word's first position
+    while (s0 + 1 < a.G && 32u * l >= s_seg[s0 + 1]) ++s0;
+    const uint32_t kmax = (uint32_t)__builtin_amdgcn_readfirstlane((int)a.k);
+    const uint32_t want = (1u << g) - 1u;             // segments 0 .. g - 1 differ, g agrees
+    WaveHits wh;
+    wh.buf = pbuf[threadIdx.x >> 6];
+    uint32_t row = 0;
+    uint32_t nx[kPiglStep];
+#pragma unroll
+    for (int u = 0; u < kPiglStep; ++u) nx[u] = p + 1 + u < a.n ? sid[p + 1 + u] : 0u;   // (not "< end": issued with sid[p])
+    for (uint64_t q0 = p + 1;; q0 += kPiglStep) {
+        if (!__ballot(q0 < end)) break;
+        uint32_t jd[kPiglStep];
+        uint64_t c[kPiglStep];
+#pragma unroll
+        for (int u = 0; u < kPiglStep; ++u) {
+            jd[u] = nx[u];
+            c[u] = q0 + u < end && live ? a.words[(uint64_t)jd[u] * a.wpr + l] : 0ull;
+            const uint64_t qn = q0 + kPiglStep + u;
+            nx[u] = qn < end ? sid[qn] : 0u;
+        }
+#pragma unroll
+        for (int u = 0; u < kPiglStep; ++u) {
+            const uint64_t x = w ^ c[u], d = (x | (x >> 1)) & pm;
+            uint32_t dd = (uint32_t)__popcll(d);
+#pragma unroll
+            for (int o = LG / 2; o; o >>= 1) dd += __shfl_xor(dd, o);
+            const bool near = (q0 + u < end) & (dd <= kmax);
+            if (!__ballot(near)) continue;
+            // g must be the first segment the rows agree on: each lane marks the segments of its
+            // word's differing positions (ascending, so the segment index only moves up)
+            uint32_t segs = 0;
+            if (near) {
+                uint32_t sgi = s0;
+                for (uint64_t m = d; m; m &= m - 1ull) {
+                    const uint32_t pos = 32u * l + ((uint32_t)__ffsll((long long)m) - 1u) / 2u;
+                    while (sgi + 1 < a.G && pos >= s_seg[sgi + 1]) ++sgi;
+                    segs |= 1u << sgi;
+                }
+            }
+#pragma unroll
+            for (int o = LG / 2; o; o >>= 1) segs |= __shfl_xor(segs, o);
+            const bool hit = near && l == 0 && (segs & (want | (1u << g))) == want;   // one lane per group
+            const uint64_t mask = __ballot(hit);
+            if (!mask) continue;
+            row += hit ? 1u : 0u;
+            if (hit && a.counts) atomicAdd(&a.counts[jd[u]], 1u);
+            hits_add(a, wh, hit, mask, id, jd[u]);
+        }
+    }
+    if (a.pairs) hits_flush(a, wh);
+    else if (lane == 0 && wh.nh) atomicAdd(&s_hits, (unsigned long long)wh.nh);
+    if (a.counts && row) atomicAdd(&a.counts[id], row);
+    __syncthreads();
+    if (threadIdx.x == 0 && s_hits) atomicAdd(a.npairs, s_hits);
+}
+
+// AUTO keeps the long form when candidates < all pairs / kPiglRatio.  Not kPigRatio: the other side
+// is the bit-plane form (slower than the MFMA tiles), and a candidate here costs a gathered row.
+// Measured (tools/probe_f4.py longsweep, profiles/r7/probe_f4_longsweep.log: pools drawn uniformly,
+// candidate fraction (k + 1) / pool, every candidate of segment 0 a hit): forced bucketed against
+// forced tiles at 100k x 150 nt, k 3: 1/16 6.48 vs 5.46 ms, 1/32 3.43 vs 5.14 ms; at 50k x 1024 nt,
+// k 16: 1/15 4.85 vs 4.22 ms, 1/30 2.72 vs 4.14 ms.  Both cross near 1/18 .. 1/20; 32 leaves the long
+// form ~1.5x ahead at the threshold, for batches whose rows no longer sit in L2 as these did.
+constexpr uint64_t kPiglRatio = 32;
+
+// returns 0 with *done = false when the auto choice hands the batch to the tiled form
+int pigl_all_pairs(const AllPairsArgs& b, uint32_t L, uint32_t P, bool forced, hipStream_t s, bool* done) {
+    *done = false;
+    PiglArgs a{};
+    a.words = b.words;
+    a.n = b.n;
+    a.wpr = b.wpr;
+    a.W = b.W;
+    a.k = b.k;
+    a.G = b.k + 1;
+    a.P = P;
+    a.counts = b.counts;
+    a.pairs = b.pairs;
+    a.max_pairs = b.max_pairs;
+    a.npairs = b.npairs;
+    a.zero_out = 1;
+    uint32_t lg = 0;
+    while ((1ull << lg) < a.n) ++lg;
+    a.nbmax = lg < 10 ? 10 : (lg > kPigMaxBits ? kPigMaxBits : lg);
+    a.maxtiles = ((1u << a.nbmax) + kPigTile - 1) / kPigTile;
+    // pig_all_pairs' split: the L read positions evenly (the first L % G segments one longer, a
+    // segment may be empty when L < G), the alias position L (P = L + 1) in the last
+    const uint32_t Lr = P < L ? P : L;
+    for (uint32_t g = 0, pos = 0; g < a.G; ++g) {
+        uint32_t len = Lr / a.G + (g < Lr % a.G ? 1u : 0u);
+        if (g + 1 == a.G) len = P - pos;
+        a.nb[g] = 2 * len < a.nbmax ? 2 * len : a.nbmax;
+        if (2 * len <= a.nbmax) a.exact |= 1u << g;
+        a.seg[g] = pos;
+        pos += len;
+    }
+    a.seg[a.G] = P;
+    const size_t hist_n = (size_t)a.G << a.nbmax, tiles_n = (size_t)a.G * a.maxtiles;
+    const size_t need = tiles_n * 8 + a.G * 8 + (hist_n + 2) * 4 + tiles_n * 4 + 64 + (size_t)a.G * a.n * 8;
+    PigHold hold;
+    bool have = false;
+    int rc = hold.acquire(b.words, need, forced, s, a.npairs, a.counts, a.n, &have);
+    if (rc || !have) return rc;
+    PigScratch& ps = *hold.ps;
+    a.tile_cand = (uint64_t*)ps.p;
+    a.cand = a.tile_cand + tiles_n;
+    a.hist = (uint32_t*)(a.cand + a.G);
+    a.done = a.hist + hist_n;                 // zeroed with hist
+    a.tile_cnt = a.done + 2;
+    a.sid = a.tile_cnt + tiles_n;
+    a.rank = a.sid + (size_t)a.G * a.n;
+    const unsigned rgrid = (unsigned)std::min<uint64_t>((a.n + 255) / 256, 2048);
+    const dim3 tgrid(a.maxtiles, a.G);
+    rc = ss_check(hipMemsetAsync(a.hist, 0, (hist_n + 2) * 4, s), "pigl hist reset");
+    if (!rc) {
+        hipLaunchKernelGGL(k_pigl_hist, dim3(rgrid), dim3(256), 0, s, a);
+        hipLaunchKernelGGL(k_pig_tile<PiglArgs>, tgrid, dim3(256), 0, s, a);
+        rc = ss_check(hipGetLastError(), "k_pigl_hist/tile");
+    }
+    bool use = forced;
+    if (!rc && !forced) {
+        rc = ss_check(hipMemcpyAsync(ps.h_cand, a.cand, a.G * 8, hipMemcpyDeviceToHost, s), "pigl totals");
+        if (!rc) rc = ss_check(hipStreamSynchronize(s), "pigl totals sync");
+        uint64_t cand = 0;
+        for (uint32_t g = 0; !rc && g < a.G; ++g) cand += ps.h_cand[g];
+        use = cand < a.n * (a.n - 1) / 2 / kPiglRatio;
+    }
+    if (!rc && use) {
+        hipLaunchKernelGGL(k_pig_apply<PiglArgs>, tgrid, dim3(256), 0, s, a);
+        hipLaunchKernelGGL(k_pigl_scatter, dim3(rgrid), dim3(256), 0, s, a);
+        const int lgn = a.W <= 4 ? 4 : (a.W <= 8 ? 8 : (a.W <= 16 ? 16 : 32));
+        const uint64_t pb = (a.n + 256 / lgn - 1) / (256 / lgn);
+        const dim3 pgrid((unsigned)pb, a.G);
+        if (pb > 0x7FFFFFFFull) rc = ss_fail(SS_EARG, "all-pairs: n too large");
+        else if (lgn == 4) hipLaunchKernelGGL(k_pigl_pairs<4>, pgrid, dim3(256), 0, s, a);
+        else if (lgn == 8) hipLaunchKernelGGL(k_pigl_pairs<8>, pgrid, dim3(256), 0, s, a);
+        else if (lgn == 16) hipLaunchKernelGGL(k_pigl_pairs<16>, pgrid, dim3(256), 0, s, a);
+        else hipLaunchKernelGGL(k_pigl_pairs<32>, pgrid, dim3(256), 0, s, a);
+        if (!rc) rc = ss_check(hipGetLastError(), "k_pig_apply / k_pigl_scatter / k_pigl_pairs");
+        if (!rc) *done = true;
+    }
+    const int r2 = ss_check(hipEventRecord(ps.done, s), "pig scratch event");
+    return rc ? rc : r2;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1038,7 +1319,9 @@ int ss_hamming_all_pairs(const uint64_t* d_words, uint64_t n, uint32_t L, uint32
 int ss_hamming_all_pairs_ex(const uint64_t* d_words, uint64_t n, uint32_t L, uint32_t wpr, uint32_t max_dist,
                             uint32_t* d_counts, uint32_t* d_pairs, uint64_t max_pairs, uint64_t* d_npairs,
                             uint32_t method, void* stream) {
-    if (method > SS_ALLPAIRS_PIGEONHOLE) return ss_fail(SS_EARG, "unknown all-pairs method");
+    if (method > SS_ALLPAIRS_BUCKETED) return ss_fail(SS_EARG, "unknown all-pairs method");
+    if (method == SS_ALLPAIRS_BUCKETED && max_dist + 1 > (uint32_t)kPiglMaxG)
+        return ss_fail(SS_EARG, "bucketed all-pairs needs max_dist <= 31");
     if (L > SS_MAX_NT) return ss_fail(SS_EARG, "L must be <= 1024");
     const uint32_t W = L <= 32u ? 1u : (L + 31u) / 32u;
     if (wpr < W || wpr > 32) return ss_fail(SS_EARG, "bad wpr");
@@ -1056,12 +1339,20 @@ int ss_hamming_all_pairs_ex(const uint64_t* d_words, uint64_t n, uint32_t L, uin
         cap = hipStreamCaptureStatusNone;
     }
     const bool capturing = cap != hipStreamCaptureStatusNone;
+    // BUCKETED: pig_all_pairs where it applies (W <= 4, max_dist < 16), the long form past that
+    const bool pig_fits = W <= 4 && Gw <= (uint32_t)kPigMaxG;
+    const bool pig_forced = method == SS_ALLPAIRS_PIGEONHOLE || (method == SS_ALLPAIRS_BUCKETED && pig_fits);
     const bool pig_try = n >= 2 && W <= 4 && method != SS_ALLPAIRS_TILES && !(capturing && method == SS_ALLPAIRS_AUTO) &&
-                         wpr >= W && d_words &&
-                         (method == SS_ALLPAIRS_PIGEONHOLE ? Gw <= (uint32_t)kPigMaxG
-                                                           : Gw <= (uint32_t)kPigMaxG && Pw / Gw >= 3 && n >= (1u << 15));
+                         wpr >= W && d_words && !(method == SS_ALLPAIRS_BUCKETED && !pig_fits) &&
+                         (pig_forced ? Gw <= (uint32_t)kPigMaxG
+                                     : Gw <= (uint32_t)kPigMaxG && Pw / Gw >= 3 && n >= (1u << 15));
+    // the long form: forced past pig_all_pairs' range; auto for W >= 5 and a batch large enough to
+    // pay the host read of the totals (never under capture, as above)
+    const bool pigl_try = n >= 2 && d_words && Gw <= (uint32_t)kPiglMaxG &&
+                          (method == SS_ALLPAIRS_BUCKETED ? !pig_fits
+                                                          : method == SS_ALLPAIRS_AUTO && !capturing && W >= 5 && n >= (1u << 15));
     int rc = SS_OK;
-    if (!pig_try) {
+    if (!pig_try && !pigl_try) {
         rc = ss_check(hipMemsetAsync(d_npairs, 0, sizeof(uint64_t), s), "npairs reset");
         if (!rc && d_counts && n) rc = ss_check(hipMemsetAsync(d_counts, 0, n * sizeof(uint32_t), s), "counts reset");
     }
@@ -1083,7 +1374,12 @@ int ss_hamming_all_pairs_ex(const uint64_t* d_words, uint64_t n, uint32_t L, uin
     // auto: segments of >= 3 nt and a batch large enough to pay the host read of the totals
     if (pig_try) {
         bool done = false;
-        rc = pig_all_pairs(a, L, Pw, method == SS_ALLPAIRS_PIGEONHOLE, s, &done);
+        rc = pig_all_pairs(a, L, Pw, pig_forced, s, &done);
+        if (rc || done) return rc;
+    }
+    if (pigl_try) {
+        bool done = false;
+        rc = pigl_all_pairs(a, L, Pw, method == SS_ALLPAIRS_BUCKETED, s, &done);
         if (rc || done) return rc;
     }
     if (W <= 4) {
