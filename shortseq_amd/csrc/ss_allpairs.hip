@@ -170,7 +170,7 @@ __global__ __launch_bounds__(256) void k_allpairs(AllPairsArgs a) {
 // Block: 4 waves x RB row blocks of 32 rows = S rows (A fragments in registers), the S columns
 // of the paired tile staged in LDS as packed words; per 32-column block each wave builds its B
 // fragments once and runs RB x KS MFMAs.  A hit needs D >= P - k; the 16 results of a tile are
-// OR-reduced (bit 7 after a 128 - thr bias) and tested with one ballot, so the (rare) hit path runs
+// OR-reduced (bits 7-8 after a 128 - thr bias) and tested with one ballot, so the (rare) hit path runs
 // only for tiles that have one.
 // Rows / columns past n get zero fragments (D = 0); the hit path checks indices.
 // ------------------------------------------------------------------------------------------------
@@ -193,7 +193,7 @@ __device__ __forceinline__ void onehot_frag(uint64_t word, bool valid, uint32_t 
 }
 
 // Hit path of one 32 x 32 result tile (st = its 16 result registers per lane, [reg][lane], hit =
-// bit 7): index checks, LDS row / column counts, wave-aggregated pair append.
+// result >= 128: bit 7 or 8): index checks, LDS row / column counts, wave-aggregated pair append.
 __device__ __noinline__ void ap_hits(const AllPairsArgs& a, const int* st, uint32_t rl0, uint32_t cl, uint64_t row0,
                                      uint64_t col0, bool diag, uint32_t* rowcnt, uint32_t* colcnt,
                                      unsigned long long* blkhits) {
@@ -202,7 +202,7 @@ __device__ __noinline__ void ap_hits(const AllPairsArgs& a, const int* st, uint3
     for (int q = 0; q < 16; ++q) {
         const uint32_t rl = rl0 + (q & 3) + 8 * (q >> 2) + 4 * h;
         const uint64_t i = row0 + rl, j = col0 + cl;
-        bool hit = (st[q * 64 + lane] & 128) && i < a.n && j < a.n;
+        bool hit = (st[q * 64 + lane] & 0x180) && i < a.n && j < a.n;
         if (diag) hit = hit && j > i;
         const uint64_t mask = __ballot(hit);
         if (!mask) continue;
@@ -302,9 +302,11 @@ __global__ __launch_bounds__(256) void k_allpairs_mfma(AllPairsArgs a, uint32_t 
         frag(rw, i < a.n, A[rb]);
     }
     __syncthreads();
-    // hit iff matches >= thr.  The accumulators start at 128 - thr, so a hit is bit 7 of the
-    // result (results stay in [96, 160]) and one OR-reduction of the 16 registers tests a tile.
-    // thr <= 0 (max distance >= P): every pair hits; thr = 0 flags them all.
+    // hit iff matches >= thr.  The accumulators start at 128 - thr, so a hit is a result >= 128.
+    // thr lies in [0, 8 KS] and matches in [0, 8 KS], 8 KS <= 128, so results lie in [0, 256] (256:
+    // identical 128-position rows at max distance >= 128): result >= 128 is bit 7 or bit 8, and an
+    // OR-reduction of the 16 non-negative registers has one of the two set exactly when one of them is
+    // >= 128, so one ballot tests a tile.  Max distance >= P: thr = 0 over the P positions, every pair hits.
     const int thr = max(0, (int)P - (int)a.k) + (TAB ? 8 * KS - (int)P : 0);
     v16i32 Cinit;
 #pragma unroll
@@ -329,7 +331,7 @@ __global__ __launch_bounds__(256) void k_allpairs_mfma(AllPairsArgs a, uint32_t 
 #pragma unroll
                 for (int q = 0; q < 16; ++q) any_all |= D[q];
             }
-            if (!__ballot(any_all & 128)) continue;
+            if (!__ballot(any_all & 0x180)) continue;
         }
 #pragma unroll
         for (int rb = 0; rb < RB; ++rb) {
@@ -339,7 +341,7 @@ __global__ __launch_bounds__(256) void k_allpairs_mfma(AllPairsArgs a, uint32_t 
             int any = D[0];
 #pragma unroll
             for (int q = 1; q < 16; ++q) any |= D[q];
-            if (!__ballot(any & 128)) continue;
+            if (!__ballot(any & 0x180)) continue;
             // hit path (rare): the 16 results go through a per-wave LDS stash into an out-of-line
             // loop, so the common path keeps its registers
             int* st = stash + wave * 1024;
@@ -1320,7 +1322,7 @@ int ss_hamming_all_pairs_ex(const uint64_t* d_words, uint64_t n, uint32_t L, uin
                             uint32_t* d_counts, uint32_t* d_pairs, uint64_t max_pairs, uint64_t* d_npairs,
                             uint32_t method, void* stream) {
     if (method > SS_ALLPAIRS_BUCKETED) return ss_fail(SS_EARG, "unknown all-pairs method");
-    if (method == SS_ALLPAIRS_BUCKETED && max_dist + 1 > (uint32_t)kPiglMaxG)
+    if (method == SS_ALLPAIRS_BUCKETED && max_dist >= (uint32_t)kPiglMaxG)
         return ss_fail(SS_EARG, "bucketed all-pairs needs max_dist <= 31");
     if (L > SS_MAX_NT) return ss_fail(SS_EARG, "L must be <= 1024");
     const uint32_t W = L <= 32u ? 1u : (L + 31u) / 32u;
@@ -1329,7 +1331,13 @@ int ss_hamming_all_pairs_ex(const uint64_t* d_words, uint64_t n, uint32_t L, uin
     if (n >= (1ull << 32)) return ss_fail(SS_EARG, "n must be < 2^32");
     hipStream_t s = (hipStream_t)stream;
     // the pigeonhole form (tried first when it may apply) zeroes the outputs in its first kernel
-    const uint32_t Pw = L + 1 < 32u * W ? L + 1 : 32u * W, Gw = max_dist + 1;
+    const uint32_t Pw = L + 1 < 32u * W ? L + 1 : 32u * W;
+    // the methods' ranges are the caller's max_dist (forced methods refuse by it); the work below runs
+    // on max_dist clamped to Pw (no distance exceeds the Pw compared positions, so the results are
+    // the same), which keeps Gw = max_dist + 1 in [1, Pw + 1]: max_dist = 2^32 - 1 would wrap it to 0
+    const bool pig_range = max_dist < (uint32_t)kPigMaxG, pigl_range = max_dist < (uint32_t)kPiglMaxG;
+    if (max_dist > Pw) max_dist = Pw;
+    const uint32_t Gw = max_dist + 1;
     // AUTO on a stream being captured into a hipGraph stays on the tiles: the pigeonhole decision
     // allocates and reads the candidate totals back (a host sync), neither of which a capture allows
     // (the entry point was capturable before AUTO existed)
@@ -1340,15 +1348,14 @@ int ss_hamming_all_pairs_ex(const uint64_t* d_words, uint64_t n, uint32_t L, uin
     }
     const bool capturing = cap != hipStreamCaptureStatusNone;
     // BUCKETED: pig_all_pairs where it applies (W <= 4, max_dist < 16), the long form past that
-    const bool pig_fits = W <= 4 && Gw <= (uint32_t)kPigMaxG;
+    const bool pig_fits = W <= 4 && pig_range;
     const bool pig_forced = method == SS_ALLPAIRS_PIGEONHOLE || (method == SS_ALLPAIRS_BUCKETED && pig_fits);
     const bool pig_try = n >= 2 && W <= 4 && method != SS_ALLPAIRS_TILES && !(capturing && method == SS_ALLPAIRS_AUTO) &&
                          wpr >= W && d_words && !(method == SS_ALLPAIRS_BUCKETED && !pig_fits) &&
-                         (pig_forced ? Gw <= (uint32_t)kPigMaxG
-                                     : Gw <= (uint32_t)kPigMaxG && Pw / Gw >= 3 && n >= (1u << 15));
+                         (pig_forced ? pig_range : pig_range && Pw / Gw >= 3 && n >= (1u << 15));
     // the long form: forced past pig_all_pairs' range; auto for W >= 5 and a batch large enough to
     // pay the host read of the totals (never under capture, as above)
-    const bool pigl_try = n >= 2 && d_words && Gw <= (uint32_t)kPiglMaxG &&
+    const bool pigl_try = n >= 2 && d_words && pigl_range &&
                           (method == SS_ALLPAIRS_BUCKETED ? !pig_fits
                                                           : method == SS_ALLPAIRS_AUTO && !capturing && W >= 5 && n >= (1u << 15));
     int rc = SS_OK;
@@ -1369,7 +1376,7 @@ int ss_hamming_all_pairs_ex(const uint64_t* d_words, uint64_t n, uint32_t L, uin
     a.pairs = d_pairs;
     a.max_pairs = d_pairs ? max_pairs : 0;
     a.npairs = (unsigned long long*)d_npairs;
-    if (method == SS_ALLPAIRS_PIGEONHOLE && (W > 4 || max_dist + 1 > (uint32_t)kPigMaxG))
+    if (method == SS_ALLPAIRS_PIGEONHOLE && (W > 4 || !pig_range))
         return ss_fail(SS_EARG, "pigeonhole all-pairs needs L <= 128 and max_dist < 16");
     // auto: segments of >= 3 nt and a batch large enough to pay the host read of the totals
     if (pig_try) {

@@ -60,6 +60,7 @@ def test_all_pairs_gpu(gpu, oracle, L, n, k):
     if total > 4:
         _, p3, total3 = B.hamming_all_pairs(d, L, k, counts=False, max_pairs=3)
         assert total3 == total and p3.shape[0] == 3
+        assert {tuple(int(x) for x in q) for q in p3.cpu().numpy()} <= set(pairs_e)
 
 
 @pytest.mark.gpu
