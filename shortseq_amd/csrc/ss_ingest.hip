@@ -915,6 +915,16 @@ struct ss_ingest {
 
 namespace {
 
+// a table's reset words queued for the next flush_prep (ss_counter_reset_host)
+int queue_reset(ss_ingest* g, ss_counter* t) {
+    unsigned long long* p[3];
+    unsigned long long v[3];
+    const int rc = ss_counter_reset_host(t, p, v);
+    g->prep_p.insert(g->prep_p.end(), p, p + 3);
+    g->prep_v.insert(g->prep_v.end(), v, v + 3);
+    return rc;
+}
+
 // a pooled table of this capacity, preferring one whose key width W1 (its key-word array) and
 // partition workspace (rows) already fit: a mismatch reallocates them at the first insert (hipFree +
 // hipMalloc, 0.3-0.4 ms per class table on the f2 batch when two classes swapped tables of one size)
@@ -933,13 +943,7 @@ int table_get(ss_ingest* g, uint64_t cap, uint32_t W1, uint64_t rows, ss_counter
     if (best < g->pool.size()) {
         *out = g->pool[best].second;
         g->pool.erase(g->pool.begin() + (long)best);
-        if (!g->defer_prep) return ss_counter_reset(*out, g->stream);
-        unsigned long long* p[3];
-        unsigned long long v[3];
-        const int rc = ss_counter_reset_host(*out, p, v);
-        g->prep_p.insert(g->prep_p.end(), p, p + 3);
-        g->prep_v.insert(g->prep_v.end(), v, v + 3);
-        return rc;
+        return g->defer_prep ? queue_reset(g, *out) : ss_counter_reset(*out, g->stream);
     }
     return ss_counter_create(cap, out);
 }
@@ -1134,6 +1138,16 @@ int group_room(ss_ingest* g, Group& gr, uint64_t m, uint64_t need) {
     return SS_OK;
 }
 
+// a table ran full: the counts are void until a reset (estimated: it was sized by its class's distinct-key estimate)
+int fail_full(ss_ingest* g, bool estimated) {
+    g->failed = true;
+    return ss_fail(SS_EFULL, estimated ? "ingest: a length class's table ran full (its distinct-key estimate was low); "
+                                         "count again with ss_ingest_set_exact"
+                                       : "ingest: a length class's table ran full; count again with ss_ingest_set_exact");
+}
+
+int fail_earlier() { return ss_fail(SS_EFULL, "ingest: an earlier add ran a table full; reset and count again"); }
+
 // the deferred fold of a read-order chunk's scratch into its class tables (see ss_ingest::pend); one
 // sync for the tables' overflow words (sized from the sketch as for an immediate fold)
 int flush_pending(ss_ingest* g) {
@@ -1149,11 +1163,7 @@ int flush_pending(ss_ingest* g) {
     if (!rc) rc = ss_check(hipStreamSynchronize(s), "ingest deferred fold");
     if (rc) return rc;
     for (uint32_t W = 2; W < 6; ++W)
-        if (g->h_bad[W]) {
-            g->failed = true;
-            return ss_fail(SS_EFULL, "ingest: a length class's table ran full (its distinct-key estimate was low); "
-                                     "count again with ss_ingest_set_exact");
-        }
+        if (g->h_bad[W]) return fail_full(g, true);
     return SS_OK;
 }
 
@@ -1168,6 +1178,65 @@ void spec_wait(ss_ingest* g) {
     if (g->spec_inflight) (void)hipEventSynchronize(g->ev_spec);
     g->spec_inflight = false;
     g->spec_valid = false;
+}
+
+// The results' ordering, queued on s: the groups' entries' first reads marked in the read map (g->slot:
+// NB words, zeroed by the caller), every entry ranked into g->ordered by its first read, the ordered
+// entries' word offsets, the rows gathered into the pinned result buffer (ol).  sd null (the finish):
+// group q holds grs[q]->m entries, K in all.  sd = the speculative finish's device words: the counts stay
+// on the device (class W's at sd[W], their total at sd[6]); a group's capacity and K only bound them.
+int queue_order(ss_ingest* g, hipStream_t s, const std::vector<Group*>& grs, GDesc* h_desc, uint64_t* sd, uint64_t NB,
+                uint64_t K, const OutLayout& ol) {
+    unsigned long long* bits = (unsigned long long*)g->slot.p;
+    const GDesc* gd = g->gdesc.p;
+    const uint64_t* dK = sd ? sd + 6 : nullptr;
+    const uint64_t empty_at = g->empty_count ? g->empty_first : kNoSlot;
+    const uint64_t* none = nullptr;
+    // a group's entry bound, and its entry count on the device (the host-sized grids cover m + 1 entries)
+    auto bound = [&](const Group& gr) { return sd ? gr.cap + 1 : gr.m; };
+    auto count = [&](const Group& gr) { return sd ? (const uint64_t*)(sd + gr.W1 - 1) : none; };
+    for (size_t q = 0; q < grs.size(); ++q) {
+        const Group& gr = *grs[q];
+        hipLaunchKernelGGL(k_mark, dim3(grid_of(bound(gr) + (sd ? 0 : 1), 256)), dim3(256), 0, s, gr.first.p, bound(gr),
+                           gr.rowmap.p, kNoSlot, bits, count(gr));
+        h_desc[q] = {gr.words.p, gr.counts.p, gr.W1, gr.L};
+    }
+    if (g->empty_count) hipLaunchKernelGGL(k_mark, dim3(1), dim3(256), 0, s, none, (uint64_t)0, none, empty_at, bits, none);
+    if (sd) hipLaunchKernelGGL(k_spec_total, dim3(1), dim3(64), 0, s, sd, g->empty_count ? 1ull : 0ull, none);
+    if (!grs.empty()) {
+        const int rc = ss_check(hipMemcpyAsync(g->gdesc.p, h_desc, grs.size() * sizeof(GDesc), hipMemcpyHostToDevice, s),
+                                sd ? "spec desc" : "ingest desc");
+        if (rc) return rc;
+    }
+    // marked reads before each read-map word (read order = dict order); woff holds that prefix first
+    // (it becomes the word offsets below)
+    hipLaunchKernelGGL((k_scan_count<0>), dim3(kScanBlocks), dim3(256), 0, s, g->slot.p, NB, gd, g->scan.p, none);
+    hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(256), 0, s, g->scan.p);
+    hipLaunchKernelGGL((k_scan_apply<0>), dim3(kScanBlocks), dim3(256), 0, s, g->slot.p, NB, gd, g->scan.p, g->woff.p, none);
+    const uint64_t ocap = sd ? K : ~0ull;
+    for (size_t q = 0; q < grs.size(); ++q) {
+        const Group& gr = *grs[q];
+        hipLaunchKernelGGL(k_rank, dim3(grid_of(bound(gr) + (sd ? 0 : 1), 256)), dim3(256), 0, s, gr.first.p, bound(gr),
+                           gr.rowmap.p, (uint32_t)q, kNoSlot, bits, g->woff.p, g->ordered.p, count(gr), ocap);
+    }
+    if (g->empty_count)
+        hipLaunchKernelGGL(k_rank, dim3(1), dim3(256), 0, s, none, (uint64_t)0, none, 0u, empty_at, bits, g->woff.p,
+                           g->ordered.p, none, ocap);
+    // word offsets of the ordered entries (K on the device: past the bound the gather refuses)
+    hipLaunchKernelGGL((k_scan_count<1>), dim3(kScanBlocks), dim3(256), 0, s, g->ordered.p, K, gd, g->scan.p, dK);
+    hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(256), 0, s, g->scan.p);
+    hipLaunchKernelGGL((k_scan_apply<1>), dim3(kScanBlocks), dim3(256), 0, s, g->ordered.p, K, gd, g->scan.p, g->woff.p, dK);
+    // The speculative finish, up to a few million entries: the rows take about as long as the verify
+    // beside them, so few waves, and the verify keeps the chip; past that the gather is the call's
+    // bound and takes the full grid
+    const uint64_t* ord = g->ordered.p;
+    if (sd && K <= kGatherWavesMax) {
+        hipLaunchKernelGGL(k_gather_host_waves, dim3(kGatherBlocks), dim3(256), 0, s, ord, K, gd, g->woff.p, g->empty_count, ol);
+        return SS_OK;
+    }
+    if (K >= (1ull << 31) * 256) return ss_fail(SS_EARG, "ingest: too many distinct keys for one gather");
+    hipLaunchKernelGGL(k_gather_host, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, s, ord, K, gd, g->woff.p, g->empty_count, ol);
+    return SS_OK;
 }
 
 // the speculative finish of a first read-order chunk (see ss_ingest::spec_stream); need[W]: the class's
@@ -1203,58 +1272,14 @@ int spec_launch(ss_ingest* g, const uint64_t* need, uint64_t N) {
         (rc = g->out_host.ensure(out_bytes)))
         return rc;
     uint64_t* sd = g->spec_dev.p;
-    unsigned long long* bits = (unsigned long long*)g->slot.p;
     if ((rc = ss_check(hipMemsetAsync(sd, 0, 13 * 8, ss), "spec reset")) ||
         (rc = ss_check(hipMemsetAsync(g->slot.p, 0, NB * 8, ss), "spec read map reset")))
         return rc;
     if ((rc = ss_classes_flat_extract(g->fpt, g->pend_S, g->pend_fc, g->pend_base, fo, g->zero32.p, ss))) return rc;
-    for (size_t q = 0; q < cls.size(); ++q) {
-        Group& gr = *cls[q];
-        const uint64_t cap = gr.cap + 1;
-        hipLaunchKernelGGL(k_mark, dim3(grid_of(cap, 256)), dim3(256), 0, ss, gr.first.p, cap, gr.rowmap.p, kNoSlot, bits,
-                           (const uint64_t*)(sd + gr.W1 - 1));
-        g->h_gdesc[q] = {gr.words.p, gr.counts.p, gr.W1, gr.L};
-    }
-    const uint64_t empty_at = g->empty_count ? g->empty_first : kNoSlot;
-    if (g->empty_count)
-        hipLaunchKernelGGL(k_mark, dim3(1), dim3(256), 0, ss, (const uint64_t*)nullptr, (uint64_t)0,
-                           (const uint64_t*)nullptr, empty_at, bits, (const uint64_t*)nullptr);
-    hipLaunchKernelGGL(k_spec_total, dim3(1), dim3(64), 0, ss, sd, g->empty_count ? 1ull : 0ull, (const uint64_t*)nullptr);
-    if ((rc = ss_check(hipMemcpyAsync(g->gdesc.p, g->h_gdesc, cls.size() * sizeof(GDesc), hipMemcpyHostToDevice, ss),
-                       "spec desc")))
-        return rc;
-    hipLaunchKernelGGL((k_scan_count<0>), dim3(kScanBlocks), dim3(256), 0, ss, g->slot.p, NB, (const GDesc*)g->gdesc.p,
-                       g->scan.p, (const uint64_t*)nullptr);
-    hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(256), 0, ss, g->scan.p);
-    hipLaunchKernelGGL((k_scan_apply<0>), dim3(kScanBlocks), dim3(256), 0, ss, g->slot.p, NB, (const GDesc*)g->gdesc.p,
-                       g->scan.p, g->woff.p, (const uint64_t*)nullptr);
-    for (size_t q = 0; q < cls.size(); ++q) {
-        Group& gr = *cls[q];
-        const uint64_t cap = gr.cap + 1;
-        hipLaunchKernelGGL(k_rank, dim3(grid_of(cap, 256)), dim3(256), 0, ss, gr.first.p, cap, gr.rowmap.p, (uint32_t)q,
-                           kNoSlot, bits, g->woff.p, g->ordered.p, (const uint64_t*)(sd + gr.W1 - 1), k_ub);
-    }
-    if (g->empty_count)
-        hipLaunchKernelGGL(k_rank, dim3(1), dim3(256), 0, ss, (const uint64_t*)nullptr, (uint64_t)0,
-                           (const uint64_t*)nullptr, 0u, empty_at, bits, g->woff.p, g->ordered.p, (const uint64_t*)nullptr,
-                           k_ub);
-    // word offsets of the ordered entries (K on the device; past the bound the gather refuses)
-    hipLaunchKernelGGL((k_scan_count<1>), dim3(kScanBlocks), dim3(256), 0, ss, g->ordered.p, k_ub, (const GDesc*)g->gdesc.p,
-                       g->scan.p, (const uint64_t*)(sd + 6));
-    hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(256), 0, ss, g->scan.p);
-    hipLaunchKernelGGL((k_scan_apply<1>), dim3(kScanBlocks), dim3(256), 0, ss, g->ordered.p, k_ub, (const GDesc*)g->gdesc.p,
-                       g->scan.p, g->woff.p, (const uint64_t*)(sd + 6));
     g->wide = results_wide(g);
-    OutLayout ol{g->out_host.p, g->out_host.cap, sd + 6, g->scan.p + kScanBlocks, 0, (unsigned long long*)(sd + 7),
-                 g->compact, g->wide ? 1 : 0};
-    // up to a few million entries the rows take about as long as the verify beside them: few waves,
-    // and the verify keeps the chip; past that the gather is the call's bound and takes the full grid
-    if (k_ub <= kGatherWavesMax)
-        hipLaunchKernelGGL(k_gather_host_waves, dim3(kGatherBlocks), dim3(256), 0, ss, g->ordered.p, k_ub,
-                           (const GDesc*)g->gdesc.p, g->woff.p, g->empty_count, ol);
-    else
-        hipLaunchKernelGGL(k_gather_host, dim3((unsigned)((k_ub + 255) / 256)), dim3(256), 0, ss, g->ordered.p, k_ub,
-                           (const GDesc*)g->gdesc.p, g->woff.p, g->empty_count, ol);
+    const OutLayout ol{g->out_host.p, g->out_host.cap, sd + 6, g->scan.p + kScanBlocks, 0, (unsigned long long*)(sd + 7),
+                       g->compact, g->wide ? 1 : 0};
+    if ((rc = queue_order(g, ss, cls, g->h_gdesc, sd, NB, k_ub, ol))) return rc;
     hipLaunchKernelGGL(k_spec_total, dim3(1), dim3(64), 0, ss, sd, g->empty_count ? 1ull : 0ull,
                        (const uint64_t*)(g->scan.p + kScanBlocks), g->empty_count);
     rc = ss_check(hipMemcpyAsync(g->h_spec, sd + 9, 4 * 8, hipMemcpyDeviceToHost, ss), "spec sizes");
@@ -1269,38 +1294,85 @@ int spec_launch(ss_ingest* g, const uint64_t* need, uint64_t N) {
 // d_buf / d_offs / d_lens: the chunk on the device (the engine's own buffers, or the caller's for
 // ss_ingest_add_device); h_chunk / h_offs: the same bytes on the host when there (the first rejected
 // read's bytes are then taken from there, else copied back).
-int process_chunk(ss_ingest* g, const uint8_t* d_buf, const uint64_t* d_offs, const uint32_t* d_lens, uint64_t nbytes,
-                  uint64_t n, uint32_t dense_L, const std::vector<uint64_t>* h_offs, const uint8_t* h_chunk,
-                  bool spec_ok = false) {
-    spec_wait(g);                    // (its buffers are reused below; the results change)
-    if (g->failed) return ss_fail(SS_EFULL, "ingest: an earlier add ran a table full; reset and count again");
-    if (n == 0) return SS_OK;
-    if (n >= (1ull << 32)) return ss_fail(SS_EARG, "ingest: a chunk holds < 2^32 reads");
-    int frc = flush_pending(g);      // the previous chunk's deferred fold (its scratch is reused below)
-    if (frc) return frc;
-    if (g->since_spill + n > g->spill_limit) {
-        const int src = spill_counts(g);
-        if (src) return src;
+struct Chunk {
+    const uint8_t* d_buf;
+    const uint64_t* d_offs;
+    const uint32_t* d_lens;
+    uint64_t nbytes, n;
+    uint32_t dense_L;
+    const std::vector<uint64_t>* h_offs;
+    const uint8_t* h_chunk;
+    bool spec_ok = false;    // a first chunk may queue the speculative finish (add_device / add_blob)
+    uint64_t base = 0;       // global index of its first read (process_chunk: g->nreads)
+};
+struct Job {
+    uint32_t bin;            // len_bin: a length 1..32 or a length class
+    uint64_t m, start, first;
+};
+struct FixJob {
+    size_t j;
+    uint64_t off, stride, row0;   // its rows' byte offset in g->rows and stride, its first table row
+};
+// what the phases of process_chunk decide about a chunk: each field is set by one phase, read by later ones
+struct ChunkPlan {
+    std::vector<Job> jobs;        // split_chunk: the short group first
+    uint32_t spec_S = 0;          // split_chunk: the row encode is already queued, at this stride
+    // plan_classes: class W's rows start at word woff[W] of g->cls_words, its fingerprints at fpoff[W]
+    uint64_t woff[33] = {0}, fpoff[33] = {0}, cls_words = 0, cls_rows = 0;
+    uint32_t w1max = 0, wlo = 33, whi = 0;
+    bool fused = false;           // fingerprints and row maps come with the rows
+    // every read a class read of <= 5 words (or empty / too long): rows in read order at a stride of w1max words
+    bool flat = false;            // (k_encode_rows), no class ranks and no row maps in the encode
+    uint64_t need_cls[33] = {0};      // encode_classes: class W's distinct-key bound
+    uint64_t* rmap[33] = {nullptr};   // encode_classes: where the fused encode writes class W's read indices
+    std::vector<FixJob> fix_jobs;     // size_tables: the lengths to insert, their bytes of g->rows
+    uint64_t rows_bytes = 0;
+    std::vector<size_t> cls_jobs;     // size_tables: the classes to count (indices into jobs)
+    std::vector<uint64_t> cls_base;   // count_classes: each class job's first table row (the exact redo)
+    bool pend_now = false;            // count_classes: this chunk's fold deferred
+    bool by_fp() const { return fused && !cls_jobs.empty(); }   // the classes are counted by fingerprint
+};
+
+// a job's reads: its run of the split's order (a dense chunk: read i is row i)
+const uint64_t* sel_of(const ss_ingest* g, const Chunk& c, const Job& jb) { return c.dense_L ? nullptr : g->order.p + jb.start; }
+
+// count jobs over the stream and the side streams, run(q, stream) queuing job q on stream q % (kSide + 1):
+// a side stream starts behind everything queued so far, and the stream waits for every side stream
+// used, also after an error (nothing may run on past the call); returns the first error
+template <typename F>
+int fan_out(ss_ingest* g, size_t count, F run) {
+    int rc = SS_OK, used = 0;
+    if (count > 1) rc = ss_check(hipEventRecord(g->ev_fork, g->stream), "ingest fork");
+    for (size_t q = 0; q < count && !rc; ++q) {
+        const int k = (int)(q % (ss_ingest::kSide + 1));
+        hipStream_t cs = k ? g->side[k - 1] : g->stream;
+        if (k > used) {
+            rc = ss_check(hipStreamWaitEvent(cs, g->ev_fork, 0), "ingest fork wait");
+            used = k;
+        }
+        if (!rc) rc = run(q, cs);
     }
-    g->since_spill += n;
-    // global read indices are u64 (row maps); a table's first index is a row of its group, u32: a
-    // group about to pass kMaxRows rows is re-keyed first (group_room)
+    for (int k = 0; k < used; ++k) {
+        const int e = ss_check(hipEventRecord(g->ev_join[k], g->side[k]), "ingest join");
+        const int w = e ? e : ss_check(hipStreamWaitEvent(g->stream, g->ev_join[k], 0), "ingest join wait");
+        if (!rc) rc = w;
+    }
+    return rc;
+}
+
+// Phase 1: the reads split by length bin (one wait for the histogram) and the histogram turned into
+// jobs; a dense chunk is one job.  The first-bad and overflow words are reset around it.
+int split_chunk(ss_ingest* g, const Chunk& c, ChunkPlan& p) {
     hipStream_t s = g->stream;
-    const uint64_t base = g->nreads;
+    const uint64_t n = c.n;
     int rc = SS_OK;
-    struct Job {
-        uint32_t bin;            // len_bin: a length 1..32 or a length class
-        uint64_t m, start, first;
-    };
-    std::vector<Job> jobs;
     // first-bad words: one per length bin (a length's insert, a class's pass), the class encode's at
     // kLenBins -- all reset here, before anything that may report
     if ((rc = g->first_bad.ensure(kLenBins + 1))) return rc;
     if ((rc = ss_check(hipMemsetAsync(g->first_bad.p, 0xFF, (kLenBins + 1) * 8, s), "ingest first_bad reset"))) return rc;
-    uint32_t spec_S = 0;         // the row encode queued behind the split at this stride (gated on the device)
-    if (dense_L) {
-        if (dense_L > SS_MAX_NT) return ss_fail(SS_EARG, "ingest: dense length > 1024");
-        jobs.push_back({dense_L < 32 ? kShortBin : len_bin(dense_L), n, 0, 0});
+    if (c.dense_L) {
+        if (c.dense_L > SS_MAX_NT) return ss_fail(SS_EARG, "ingest: dense length > 1024");
+        p.jobs.push_back({c.dense_L < 32 ? kShortBin : len_bin(c.dense_L), n, 0, 0});
     } else {
         if ((rc = g->order.ensure(n)) || (rc = g->blkhist.ensure((uint64_t)kLenBins * kSplitBlocks)) ||
             (rc = g->blkfirst.ensure((uint64_t)kLenBins * kSplitBlocks)) || (rc = g->split_out.ensure(3 * kLenBins + 1)))
@@ -1308,7 +1380,7 @@ int process_chunk(ss_ingest* g, const uint8_t* d_buf, const uint64_t* d_offs, co
         // (the side stream's speculative encode below starts behind everything queued so far, not behind the split)
         const bool spec_enc = g->flat_hint != 0 && g->flat_streak >= 2;
         if (spec_enc) rc = ss_check(hipEventRecord(g->ev_fork, s), "ingest fork");
-        hipLaunchKernelGGL(k_len_count, dim3(kSplitBlocks), dim3(64), 0, s, d_lens, n, g->blkhist.p, g->blkfirst.p);
+        hipLaunchKernelGGL(k_len_count, dim3(kSplitBlocks), dim3(64), 0, s, c.d_lens, n, g->blkhist.p, g->blkfirst.p);
         hipLaunchKernelGGL(k_len_binscan, dim3(kLenBins), dim3(1024), 0, s, kSplitBlocks, g->blkhist.p, g->blkfirst.p,
                            g->split_out.p);
         hipLaunchKernelGGL(k_len_binstart, dim3(1), dim3(1024), 0, s, g->split_out.p);
@@ -1324,35 +1396,24 @@ int process_chunk(ss_ingest* g, const uint8_t* d_buf, const uint64_t* d_offs, co
         // sketches them by (a max register: a subset of the same updates), and reports only rejected
         // class reads, which every path reports.  After one chunk it is queued behind the split on the
         // stream, gated on the device by the split's own stride (a wrong guess returns at once).
-        if (!rc && g->flat_hint && !spec_enc) {
-            const uint32_t S = g->flat_hint;
-            if (!(rc = g->cls_words.ensure(n * S + 2)) && !(rc = g->cls_fps.ensure(n))) {
-                rc = ss_encode_rows_impl(d_buf, d_offs, d_lens, n, S, g->cls_words.p, g->cls_fps.p, g->hll.p,
-                                         g->first_bad.p + kLenBins, s, g->split_out.p + 3 * kLenBins);
-                if (!rc) spec_S = S;
-            }
-        }
-        bool joined = false;
-        if (!rc && spec_enc) {
-            const uint32_t S = g->flat_hint;
-            if (!(rc = g->cls_words.ensure(n * S + 2)) && !(rc = g->cls_fps.ensure(n)) &&
-                !(rc = ss_check(hipStreamWaitEvent(g->side[0], g->ev_fork, 0), "ingest fork wait"))) {
-                rc = ss_encode_rows_impl(d_buf, d_offs, d_lens, n, S, g->cls_words.p, g->cls_fps.p, g->hll.p,
-                                         g->first_bad.p + kLenBins, g->side[0], nullptr);
-                if (!rc) rc = ss_check(hipEventRecord(g->ev_join[0], g->side[0]), "ingest spec encode join");
-                // everything queued on the stream from here on runs behind the encode
-                if (!rc) rc = ss_check(hipStreamWaitEvent(s, g->ev_join[0], 0), "ingest spec encode wait");
-                joined = !rc;
-                if (!rc) spec_S = S;
-            }
+        const uint32_t S = g->flat_hint;
+        if (!rc && S && !(rc = g->cls_words.ensure(n * S + 2)) && !(rc = g->cls_fps.ensure(n)) &&
+            !(spec_enc && (rc = ss_check(hipStreamWaitEvent(g->side[0], g->ev_fork, 0), "ingest fork wait")))) {
+            rc = ss_encode_rows_impl(c.d_buf, c.d_offs, c.d_lens, n, S, g->cls_words.p, g->cls_fps.p, g->hll.p,
+                                     g->first_bad.p + kLenBins, spec_enc ? g->side[0] : s,
+                                     spec_enc ? nullptr : g->split_out.p + 3 * kLenBins);
+            if (!rc && spec_enc) rc = ss_check(hipEventRecord(g->ev_join[0], g->side[0]), "ingest spec encode join");
+            // everything queued on the stream from here on runs behind the encode
+            if (!rc && spec_enc) rc = ss_check(hipStreamWaitEvent(s, g->ev_join[0], 0), "ingest spec encode wait");
+            if (!rc) p.spec_S = S;
         }
         if (!rc) rc = ss_check(hipEventSynchronize(g->ev_split), "ingest split");
         if (rc) {
-            if (spec_enc && !joined) (void)hipStreamSynchronize(g->side[0]);   // nothing left writing the buffers
+            if (spec_enc && !p.spec_S) (void)hipStreamSynchronize(g->side[0]);   // (not joined) nothing left writing the buffers
             return rc;
         }
         const uint64_t* hh = g->h_split;
-        if (spec_S && hh[3 * kLenBins] != spec_S) spec_S = 0;    // the queued encode did nothing (or is rewritten)
+        if (p.spec_S && hh[3 * kLenBins] != p.spec_S) p.spec_S = 0;    // the queued encode did nothing (or is rewritten)
         Job shortj{kShortBin, 0, 0, kNoSlot};     // lengths 1..31: contiguous bins of the split, one job
         for (uint32_t b = 0; b < kLenBins; ++b) {
             const uint64_t m = hh[b];
@@ -1368,61 +1429,66 @@ int process_chunk(ss_ingest* g, const uint8_t* d_buf, const uint64_t* d_offs, co
             }
             if (b == 0) {
                 g->empty_count += m;
-                g->empty_first = std::min(g->empty_first, base + f);
+                g->empty_first = std::min(g->empty_first, c.base + f);
             } else if (b == kTooLongBin) {
-                if (base + f < g->bad_index) {
-                    g->bad_index = base + f;
+                if (c.base + f < g->bad_index) {
+                    g->bad_index = c.base + f;
                     g->bad_kind = SS_ETOO_LONG;
                     g->bad_bytes.clear();
                 }
             } else {
-                jobs.push_back({b, m, hh[2 * kLenBins + b], f});
+                p.jobs.push_back({b, m, hh[2 * kLenBins + b], f});
             }
         }
-        if (shortj.m) jobs.insert(jobs.begin(), shortj);
+        if (shortj.m) p.jobs.insert(p.jobs.begin(), shortj);
     }
-    const size_t nj = jobs.size();
+    const size_t nj = p.jobs.size();     // (an overflow word per job, the fingerprint scratch table's last)
     if ((rc = g->ovf.ensure(nj + 1))) return rc;
-    if (nj && (rc = ss_check(hipMemsetAsync(g->ovf.p, 0, (nj + 1) * 8, s), "ingest overflow reset"))) return rc;
-    auto live = [&](const Job& jb) { return base + jb.first <= g->bad_index; };   // may still hold the first error
-    // ---- the length classes: rows packed (W words + the length) and their distinct keys sketched ----
-    uint64_t woff[33] = {0}, fpoff[33] = {0}, cls_words = 0, cls_rows = 0;
-    uint32_t w1max = 0, wlo = 33, whi = 0;
-    for (const Job& jb : jobs) {
+    return nj ? ss_check(hipMemsetAsync(g->ovf.p, 0, (nj + 1) * 8, s), "ingest overflow reset") : SS_OK;
+}
+
+// Phase 2: where each class's rows go, and which encode writes them.  The engine's stride guess for
+// the next chunk (flat_hint / flat_streak) follows from it.
+int plan_classes(ss_ingest* g, const Chunk& c, ChunkPlan& p) {
+    for (const Job& jb : p.jobs) {
         if (jb.bin <= 32) continue;
         const uint32_t W = jb.bin - kClassBin0;
-        woff[W] = cls_words;
-        fpoff[W] = cls_rows;
-        cls_words += jb.m * (W + 1);
-        cls_rows += jb.m;
-        w1max = std::max(w1max, W + 1);
-        wlo = std::min(wlo, W);
-        whi = std::max(whi, W);
+        p.woff[W] = p.cls_words;
+        p.fpoff[W] = p.cls_rows;
+        p.cls_words += jb.m * (W + 1);
+        p.cls_rows += jb.m;
+        p.w1max = std::max(p.w1max, W + 1);
+        p.wlo = std::min(p.wlo, W);
+        p.whi = std::max(p.whi, W);
     }
-    uint64_t need_cls[33] = {0};
-    const bool fused = !dense_L && w1max && w1max <= 16;   // fingerprints and row maps come with the rows
-    // every read a class read of <= 5 words (or empty / too long): rows in read order at a stride of
-    // w1max words (k_encode_rows), no class ranks and no row maps in the encode
-    bool flat = fused && w1max <= 6;
-    for (const Job& jb : jobs) flat &= jb.bin > 32;
-    if (spec_S && !(flat && w1max == spec_S))
+    p.fused = !c.dense_L && p.w1max && p.w1max <= 16;
+    p.flat = p.fused && p.w1max <= 6;
+    for (const Job& jb : p.jobs) p.flat &= jb.bin > 32;
+    if (p.spec_S && !(p.flat && p.w1max == p.spec_S))
         return ss_fail(SS_EARG, "ingest: the device's read-order stride disagrees with the host's split");
-    if (!dense_L) {
-        g->flat_streak = flat ? (w1max == g->flat_hint ? g->flat_streak + 1 : 1u) : 0u;
-        g->flat_hint = flat ? w1max : 0u;
+    if (!c.dense_L) {
+        g->flat_streak = p.flat ? (p.w1max == g->flat_hint ? g->flat_streak + 1 : 1u) : 0u;
+        g->flat_hint = p.flat ? p.w1max : 0u;
     }
+    return SS_OK;
+}
+
+// Phase 3, the length classes: rows packed (W words + the length) by one of three encodes and their
+// distinct keys sketched; the sketch comes back (one sync) and bounds each class's keys (need_cls)
+int encode_classes(ss_ingest* g, const Chunk& c, ChunkPlan& p) {
+    hipStream_t s = g->stream;
+    int rc = SS_OK;
     // the stable split into d_order: for the lengths 1..32 (row gathers) and the per-class passes; the
     // fused class encode ranks its rows itself from k_len_binscan's per-block offsets
-    bool need_order = !dense_L && (!fused && w1max);
-    for (const Job& jb : jobs) need_order |= !dense_L && jb.bin <= 32;
+    bool need_order = !c.dense_L && (!p.fused && p.w1max);
+    for (const Job& jb : p.jobs) need_order |= !c.dense_L && jb.bin <= 32;
     if (need_order)
-        hipLaunchKernelGGL(k_len_scatter, dim3(kSplitBlocks), dim3(64), 0, s, d_lens, n, g->blkhist.p,
+        hipLaunchKernelGGL(k_len_scatter, dim3(kSplitBlocks), dim3(64), 0, s, c.d_lens, c.n, g->blkhist.p,
                            (const uint64_t*)g->split_out.p, g->order.p);
-    uint64_t* rmap[33] = {nullptr};
-    if (fused) {
+    if (p.fused) {
         // every class group's rows fit its table's u32 first index (re-keyed first otherwise) and its
         // row map has room for the chunk's rows: the encode writes their read indices there
-        for (const Job& jb : jobs) {
+        for (const Job& jb : p.jobs) {
             if (jb.bin <= 32) continue;
             Group& gr = g->groups[jb.bin];
             gr.L = 0;
@@ -1432,286 +1498,239 @@ int process_chunk(ss_ingest* g, const uint8_t* d_buf, const uint64_t* d_offs, co
                 if ((rc = group_rekey(g, gr))) return rc;
             }
             if ((rc = gr.rowmap.ensure_keep(gr.rows + jb.m, gr.rows, s))) return rc;
-            rmap[gr.W1 - 1] = gr.rowmap.p + gr.rows;
+            p.rmap[gr.W1 - 1] = gr.rowmap.p + gr.rows;
         }
     }
-    if (w1max) {
-        if ((rc = g->cls_words.ensure(cls_words))) return rc;
-        if (fused && (rc = g->cls_fps.ensure(flat ? n : cls_rows))) return rc;
-        if (flat) {
-            // (+2: k_flat_verify's quads load a row's last piece as 16 B, one word past an odd stride)
-            if ((rc = g->cls_words.ensure(n * w1max + 2))) return rc;
-            if (!spec_S)      // (else queued behind the split)
-                rc = ss_encode_rows_impl(d_buf, d_offs, d_lens, n, w1max, g->cls_words.p, g->cls_fps.p, g->hll.p,
-                                         g->first_bad.p + kLenBins, s);
-        } else if (fused) {                 // one read-order pass, the registers updated in it
-            rc = ss_encode_classes_impl(d_buf, d_offs, d_lens, n, g->blkhist.p, kSplitBlocks, woff, fpoff, rmap, base,
-                                        kClassBin0, w1max, g->cls_words.p, g->cls_fps.p, g->hll.p, g->first_bad.p + kLenBins, s);
-        } else {                            // a class per pass (longer reads, or a dense chunk)
-            for (size_t j = 0; j < nj && !rc; ++j) {
-                const Job& jb = jobs[j];
-                if (jb.bin <= 32) continue;
-                const uint32_t W = jb.bin - kClassBin0;
-                const uint64_t* sel = dense_L ? nullptr : g->order.p + jb.start;
-                rc = ss_encode_class_impl(d_buf, d_offs, d_lens, sel, dense_L, jb.m, W, g->cls_words.p + woff[W],
-                                          g->first_bad.p + jb.bin, s);
-                if (!rc) rc = ss_hll_rows_impl(g->cls_words.p + woff[W], jb.m, W + 1, g->hll.p + ((uint64_t)W << kHllLog), s);
-            }
-        }
-        // the registers come back (one sync): each class table is sized by its distinct keys so far
-        // (the sketch covers every chunk of the call), not by its rows
-        const uint64_t r0 = (uint64_t)wlo << kHllLog, nr = (uint64_t)(whi - wlo + 1) << kHllLog;
-        if (!rc) rc = ss_check(hipMemcpyAsync(g->h_hll + r0, g->hll.p + r0, nr * 4, hipMemcpyDeviceToHost, s), "ingest sketch copy");
-        if (!rc) rc = ss_check(hipStreamSynchronize(s), "ingest sketch");
-        if (rc) return rc;
-        for (const Job& jb : jobs) {
+    if (!p.w1max) return SS_OK;
+    if ((rc = g->cls_words.ensure(p.cls_words)) || (p.fused && (rc = g->cls_fps.ensure(p.flat ? c.n : p.cls_rows)))) return rc;
+    if (p.flat) {
+        // (+2: k_flat_verify's quads load a row's last piece as 16 B, one word past an odd stride)
+        if ((rc = g->cls_words.ensure(c.n * p.w1max + 2))) return rc;
+        if (!p.spec_S)      // (else queued behind the split)
+            rc = ss_encode_rows_impl(c.d_buf, c.d_offs, c.d_lens, c.n, p.w1max, g->cls_words.p, g->cls_fps.p, g->hll.p,
+                                     g->first_bad.p + kLenBins, s);
+    } else if (p.fused) {               // one read-order pass, the registers updated in it
+        rc = ss_encode_classes_impl(c.d_buf, c.d_offs, c.d_lens, c.n, g->blkhist.p, kSplitBlocks, p.woff, p.fpoff, p.rmap,
+                                    c.base, kClassBin0, p.w1max, g->cls_words.p, g->cls_fps.p, g->hll.p,
+                                    g->first_bad.p + kLenBins, s);
+    } else {                            // a class per pass (longer reads, or a dense chunk)
+        for (size_t j = 0; j < p.jobs.size() && !rc; ++j) {
+            const Job& jb = p.jobs[j];
             if (jb.bin <= 32) continue;
             const uint32_t W = jb.bin - kClassBin0;
-            const double e = hll_estimate(g->h_hll + ((uint64_t)W << kHllLog));
-            need_cls[W] = g->sizing == 1 ? ~0ull                                   // the rows bound
-                        : g->sizing == 2 ? (uint64_t)(e / 64.0) + 64                   // test: undersized
-                                         : (uint64_t)(1.2 * e) + 256;                  // ~9 sigma above the estimate
+            rc = ss_encode_class_impl(c.d_buf, c.d_offs, c.d_lens, sel_of(g, c, jb), c.dense_L, jb.m, W,
+                                      g->cls_words.p + p.woff[W], g->first_bad.p + jb.bin, s);
+            if (!rc) rc = ss_hll_rows_impl(g->cls_words.p + p.woff[W], jb.m, W + 1, g->hll.p + ((uint64_t)W << kHllLog), s);
         }
     }
-    std::vector<size_t> cls_jobs;
-    struct FixJob {
-        size_t j;
-        uint64_t off, stride, row0;   // its rows' byte offset in g->rows and stride, its first table row
-    };
-    std::vector<FixJob> fix_jobs;
-    uint64_t rows_bytes = 0;
-    // new groups' pooled tables: their resets queued (table_get) and set in one dispatch below, before
-    // the first insert; whatever is still queued goes out when this function returns
-    g->defer_prep = true;
-    struct PrepScope {
-        ss_ingest* g;
-        ~PrepScope() {
-            g->defer_prep = false;
-            if (!g->prep_p.empty()) (void)flush_prep(g);
-        }
-    } prep_scope{g};
-    for (size_t j = 0; j < nj; ++j) {
-        const Job& jb = jobs[j];
+    // the registers come back (one sync): each class table is sized by its distinct keys so far
+    // (the sketch covers every chunk of the call), not by its rows
+    const uint64_t r0 = (uint64_t)p.wlo << kHllLog, nr = (uint64_t)(p.whi - p.wlo + 1) << kHllLog;
+    if (!rc) rc = ss_check(hipMemcpyAsync(g->h_hll + r0, g->hll.p + r0, nr * 4, hipMemcpyDeviceToHost, s), "ingest sketch copy");
+    if (!rc) rc = ss_check(hipStreamSynchronize(s), "ingest sketch");
+    if (rc) return rc;
+    for (const Job& jb : p.jobs) {
+        if (jb.bin <= 32) continue;
+        const uint32_t W = jb.bin - kClassBin0;
+        const double e = hll_estimate(g->h_hll + ((uint64_t)W << kHllLog));
+        p.need_cls[W] = g->sizing == 1 ? ~0ull                                   // the rows bound
+                      : g->sizing == 2 ? (uint64_t)(e / 64.0) + 64                   // test: undersized
+                                       : (uint64_t)(1.2 * e) + 256;                  // ~9 sigma above the estimate
+    }
+    return SS_OK;
+}
+
+// Phase 4 (host work, syncs): every job's table sized, its row map grown and its workspace reserved
+int size_tables(ss_ingest* g, const Chunk& c, ChunkPlan& p) {
+    int rc = SS_OK;
+    for (size_t j = 0; j < p.jobs.size(); ++j) {
+        const Job& jb = p.jobs[j];
         const bool cls = jb.bin > 32;
-        // (the fused classes are counted together: all of them, the call raises anyway when one lies
-        // past the first rejected read)
-        if (!live(jb) && !(cls && fused)) continue;
+        // a job past the first rejected read cannot hold the first error: skipped (the fused classes
+        // are counted together: all of them, the call raises anyway when one lies past that read)
+        if (c.base + jb.first > g->bad_index && !(cls && p.fused)) continue;
         Group& gr = g->groups[jb.bin];
         gr.L = cls ? 0u : jb.bin == kShortBin ? kShortL : jb.bin;
         gr.W1 = cls ? jb.bin - kClassBin0 + 1 : 1u;
-        const uint64_t need = std::min<uint64_t>(gr.rows + jb.m, cls ? need_cls[gr.W1 - 1] : ~0ull);
+        const uint64_t need = std::min<uint64_t>(gr.rows + jb.m, cls ? p.need_cls[gr.W1 - 1] : ~0ull);
         if ((rc = group_room(g, gr, jb.m, need))) return rc;
         // (a multi-chunk FASTQ: the first row map holds the whole file's estimated rows, not a doubling per chunk)
         const uint64_t rm = gr.rowmap.cap || g->est_scale <= 1.0 ? gr.rows + jb.m : (uint64_t)((double)(gr.rows + jb.m) * g->est_scale * 1.1);
-        if ((rc = gr.rowmap.ensure_keep(std::max(rm, gr.rows + jb.m), gr.rows, s))) return rc;
-        const uint64_t* sel = dense_L ? nullptr : g->order.p + jb.start;
+        if ((rc = gr.rowmap.ensure_keep(std::max(rm, gr.rows + jb.m), gr.rows, g->stream))) return rc;
         if (cls) {
-            cls_jobs.push_back(j);     // inserted below, on the class streams
+            p.cls_jobs.push_back(j);     // inserted by count_classes
             continue;
         }
         // length 32: its rows gathered at a 16-B stride into its own run of g->rows; the short group:
-        // its keys there (8 B per read); inserted below
+        // its keys there (8 B per read); inserted by insert_fixed
         const bool shortg = jb.bin == kShortBin;
-        const uint64_t stride = shortg ? 8 : dense_L ? dense_L : (jb.bin + 15) / 16 * 16;
-        fix_jobs.push_back({j, rows_bytes, stride, gr.rows});
-        if (shortg || !dense_L) rows_bytes += (jb.m * stride + 255) & ~255ull;     // (runs 16-B aligned)
+        const uint64_t stride = shortg ? 8 : c.dense_L ? c.dense_L : (jb.bin + 15) / 16 * 16;
+        p.fix_jobs.push_back({j, p.rows_bytes, stride, gr.rows});
+        if (shortg || !c.dense_L) p.rows_bytes += (jb.m * stride + 255) & ~255ull;     // (runs 16-B aligned)
         // (+1/4: the next chunk's slightly larger share of this length reuses the workspace)
         if (jb.m >= (1u << 16) && jb.m < (1ull << 30)) (void)ss_counter_reserve(gr.table, jb.m + jb.m / 4);
         gr.rows += jb.m;
     }
-    // The lengths' inserts: every table is sized, its row map grown and its workspace reserved above
-    // (host work, syncs), so the gathers, inserts and row maps of up to kSide + 1 lengths now run on
-    // as many streams at once -- a small-RNA chunk has ~15 lengths of a few 100k reads each, whose
-    // short partition kernels left the GPU mostly idle one length after another.
-    if (!fix_jobs.empty()) {
-        if (rows_bytes && (rc = g->rows.ensure(rows_bytes))) return rc;
+    return SS_OK;
+}
+
+// Phase 5, the lengths' inserts: every table is ready (size_tables), so the gathers, inserts and row maps of
+// up to kSide + 1 lengths now run on as many streams at once -- a small-RNA chunk has ~15 lengths of a few
+// 100k reads each, whose short partition kernels left the GPU mostly idle one length after another.
+int insert_fixed(ss_ingest* g, const Chunk& c, ChunkPlan& p) {
+    if (p.fix_jobs.empty()) return SS_OK;
+    int rc = p.rows_bytes ? g->rows.ensure(p.rows_bytes) : SS_OK;
+    if (rc || (rc = flush_prep(g))) return rc;
+    return fan_out(g, p.fix_jobs.size(), [&](size_t q, hipStream_t cs) {
+        const FixJob& fj = p.fix_jobs[q];
+        const Job& jb = p.jobs[fj.j];
+        Group& gr = g->groups[jb.bin];
+        const uint64_t* sel = sel_of(g, c, jb);
+        int rc = SS_OK;
+        if (jb.bin == kShortBin) {      // the short group: keys with their length markers, one insert
+            uint64_t* keys = (uint64_t*)(g->rows.p + fj.off);
+            rc = ss_short_keys_impl(c.d_buf, c.d_offs, c.d_lens, sel, jb.m, c.dense_L, keys, g->first_bad.p + jb.bin, cs);
+            if (!rc) rc = ss_counter_insert_keys(gr.table, keys, jb.m, fj.row0, cs);
+        } else {
+            const uint8_t* src = c.d_buf;
+            if (!c.dense_L) {
+                src = g->rows.p + fj.off;
+                rc = ss_gather_rows(c.d_buf, c.nbytes, c.d_offs, sel, jb.m, jb.bin, g->rows.p + fj.off, fj.stride, cs);
+            }
+            if (!rc) rc = ss_counter_insert_fixed(gr.table, src, jb.m, jb.bin, fj.stride, fj.row0, g->first_bad.p + jb.bin, cs);
+        }
+        if (!rc) hipLaunchKernelGGL(k_rowmap, dim3(grid_of(jb.m, 256)), dim3(256), 0, cs, sel, jb.m, c.base, gr.rowmap.p + fj.row0);
+        return rc;
+    });
+}
+
+// Phase 6: the classes' rows into their tables -- by fingerprint when they came with the rows, the
+// fold done at once or deferred (ss_ingest::pend), else exactly, class beside class
+int count_classes(ss_ingest* g, const Chunk& c, ChunkPlan& p) {
+    hipStream_t s = g->stream;
+    const size_t nj = p.jobs.size();
+    int rc = SS_OK;
+    p.cls_base.assign(nj, 0);
+    if (!p.by_fp()) {
         if ((rc = flush_prep(g))) return rc;
-        int used = 0;
-        if (fix_jobs.size() > 1) rc = ss_check(hipEventRecord(g->ev_fork, s), "ingest fork");
-        for (size_t q = 0; q < fix_jobs.size() && !rc; ++q) {
-            const FixJob& fj = fix_jobs[q];
-            const Job& jb = jobs[fj.j];
-            Group& gr = g->groups[jb.bin];
-            const int k = (int)(q % (ss_ingest::kSide + 1));
-            hipStream_t cs = s;
-            if (k > 0) {
-                cs = g->side[k - 1];
-                if (k > used) {
-                    rc = ss_check(hipStreamWaitEvent(cs, g->ev_fork, 0), "ingest fork wait");
-                    used = k;
-                }
-            }
-            const uint64_t* sel = dense_L ? nullptr : g->order.p + jb.start;
-            const uint8_t* src = d_buf;
-            if (jb.bin == kShortBin) {      // the short group: keys with their length markers, one insert
-                uint64_t* keys = (uint64_t*)(g->rows.p + fj.off);
-                if (!rc) rc = ss_short_keys_impl(d_buf, d_offs, d_lens, sel, jb.m, dense_L, keys, g->first_bad.p + jb.bin, cs);
-                if (!rc) rc = ss_counter_insert_keys(gr.table, keys, jb.m, fj.row0, cs);
-            } else {
-                if (!rc && !dense_L) {
-                    src = g->rows.p + fj.off;
-                    rc = ss_gather_rows(d_buf, nbytes, d_offs, sel, jb.m, jb.bin, g->rows.p + fj.off, fj.stride, cs);
-                }
-                if (!rc) rc = ss_counter_insert_fixed(gr.table, src, jb.m, jb.bin, fj.stride, fj.row0, g->first_bad.p + jb.bin, cs);
-            }
-            if (!rc)
-                hipLaunchKernelGGL(k_rowmap, dim3(grid_of(jb.m, 256)), dim3(256), 0, cs, sel, jb.m, base,
-                                   gr.rowmap.p + fj.row0);
-        }
-        for (int k = 0; k < used; ++k) {     // join (also after an error: nothing may run on past the call)
-            const int e = ss_check(hipEventRecord(g->ev_join[k], g->side[k]), "ingest join");
-            const int w = e ? e : ss_check(hipStreamWaitEvent(s, g->ev_join[k], 0), "ingest join wait");
-            if (!rc) rc = w;
-        }
-        if (rc) return rc;
-    }
-    g->defer_prep = false;
-    std::vector<uint64_t> cls_base(nj, 0);     // each class job's first table row (the exact redo)
-    bool pend_now = false;                     // this chunk's fold deferred (set below)
-    if (!(!cls_jobs.empty() && fused) && (rc = flush_prep(g))) return rc;
-    if (!cls_jobs.empty() && fused) {
-        // the classes' rows counted by fingerprint in one scratch table, checked against their
-        // fingerprints' first rows and folded into the class tables (ss_classes_verify_fold); a
-        // fingerprint shared by two keys sends the classes to the exact path below, after the sync
-        uint64_t need_all = flat ? 1 : 0;     // (the zero rows' entry)
-        std::vector<ss_class_rows> cr;
-        ss_flat_class fc[6] = {};
-        for (size_t j : cls_jobs) {
-            const Job& jb = jobs[j];
-            Group& gr = g->groups[jb.bin];
-            need_all += std::min<uint64_t>(jb.m, need_cls[gr.W1 - 1]);
-            cr.push_back({gr.table, g->cls_words.p + woff[gr.W1 - 1], jb.m, gr.rows, gr.W1});
-            if (flat) fc[gr.W1 - 1] = {gr.table, gr.rows, gr.rowmap.p + gr.rows};
-        }
-        // twice the estimate; past 2^24 slots 1.5 times: the per-slot passes (a 64-B representative per
-        // slot, the extract) then cost more than a fuller table's longer probes (2^24-pool batch
-        // 20.8 -> 19.4 ms; at 2^20 the fuller 2^21 table was 0.4 ms slower, libab_f2_lf15_u2{0,4}.log)
-        uint64_t fwant = pow2_at_least(2 * need_all + 2);
-        if (fwant > (1ull << 24)) fwant = pow2_at_least(need_all + need_all / 2 + 2);
-        const uint64_t fcap = std::min<uint64_t>(1ull << 32, std::max<uint64_t>(1ull << 19, fwant));
-        // grow-only with hysteresis: a stream whose per-chunk estimates cross a power of
-        // two keeps its table; only a table 8x too large (its per-slot passes, reps and fold, scale
-        // with the capacity) is replaced by a smaller one
-        if (g->fpt && (ss_counter_capacity(g->fpt) < fcap || ss_counter_capacity(g->fpt) >= 8 * fcap)) {
-            (void)hipStreamSynchronize(s);
-            ss_counter_destroy(g->fpt);
-            g->fpt = nullptr;
-        }
-        if (!g->fpt && (rc = ss_counter_create(fcap, &g->fpt))) return rc;
-        {   // the scratch table's reset with the class tables' queued ones, one dispatch
-            unsigned long long* p[3];
-            unsigned long long v[3];
-            if ((rc = ss_counter_reset_host(g->fpt, p, v))) return rc;
-            g->prep_p.insert(g->prep_p.end(), p, p + 3);
-            g->prep_v.insert(g->prep_v.end(), v, v + 3);
-            if ((rc = flush_prep(g))) return rc;
-        }
-        if ((rc = g->cls_flag.ensure(1))) return rc;
-        // (sizing modes 3 / 4, test hooks: the flag starts raised, as if two keys shared a fingerprint;
-        // 4 keeps the deferred fold and the speculative finish, so the flag is found after they were queued)
-        rc = ss_check(hipMemsetAsync(g->cls_flag.p, g->sizing == 3 || g->sizing == 4 ? 1 : 0, 4, s),
-                      "ingest class flag reset");
-        if (!rc && !flat) rc = ss_counter_insert_keys(g->fpt, g->cls_fps.p, cls_rows, 0, s);
-        if (!rc && !flat) rc = ss_classes_verify_fold(g->fpt, g->cls_fps.p, cr.data(), (uint32_t)cr.size(), g->cls_flag.p, s);
-        // the fold is deferred when every class of the chunk starts from an empty table (see pend)
-        bool defer = flat && (g->sizing == 0 || g->sizing >= 4);
-        for (uint32_t W = 2; W < 6; ++W) defer &= !fc[W].table || fc[W].base == 0;
-        if (!rc && flat) rc = ss_counter_insert_keys(g->fpt, g->cls_fps.p, n, 0, s);
-        if (!rc && flat && defer) {
-            // a first chunk of an add_device / add_blob also queues the speculative finish beside the verify
-            const bool spec = spec_ok && base == 0 && g->bad_index == kNoSlot;
-            rc = ss_classes_flat_verify(g->fpt, g->cls_words.p, w1max, n, g->cls_fps.p, g->cls_flag.p, s,
-                                        spec ? (void*)g->ev_reps : nullptr);
-            if (!rc) {      // pending once the flag comes back clear (checked after the sync below)
-                g->pend_S = w1max;
-                g->pend_base = base;
-                for (uint32_t W = 0; W < 6; ++W) g->pend_fc[W] = fc[W];
-            }
-            if (!rc && spec) rc = spec_launch(g, need_cls, base + n);
-        } else if (!rc && flat) {
-            rc = ss_classes_flat_verify_fold(g->fpt, g->cls_words.p, w1max, n, g->cls_fps.p, fc, base, g->cls_flag.p, s);
-        }
-        pend_now = !rc && flat && defer;
-        if (!rc) rc = ss_counter_overflow(g->fpt, g->ovf.p + nj, s);
-        for (size_t q = 0; q < cls_jobs.size() && !rc; ++q) {
-            const size_t j = cls_jobs[q];
-            const Job& jb = jobs[j];
-            Group& gr = g->groups[jb.bin];
-            cls_base[j] = gr.rows;
-            rc = ss_counter_overflow(gr.table, g->ovf.p + j, s);
-            gr.rows += jb.m;           // (their row map: written by the encode, or by the fold for new keys)
-        }
-        if (rc) return rc;
-    } else if (!cls_jobs.empty()) {
         // every table of a class job is sized, reset and its row map grown on the main stream above
-        int used = 0;
-        if (cls_jobs.size() > 1) rc = ss_check(hipEventRecord(g->ev_fork, s), "ingest fork");
-        for (size_t q = 0; q < cls_jobs.size() && !rc; ++q) {
-            const size_t j = cls_jobs[q];
-            const Job& jb = jobs[j];
+        return fan_out(g, p.cls_jobs.size(), [&](size_t q, hipStream_t cs) {
+            const size_t j = p.cls_jobs[q];
+            const Job& jb = p.jobs[j];
             Group& gr = g->groups[jb.bin];
-            const int k = (int)(q % (ss_ingest::kSide + 1));
-            hipStream_t cs = s;
-            if (k > 0) {
-                cs = g->side[k - 1];
-                if (k > used) {
-                    rc = ss_check(hipStreamWaitEvent(cs, g->ev_fork, 0), "ingest fork wait");
-                    used = k;
-                }
-            }
-            if (!rc) rc = ss_counter_insert_words(gr.table, g->cls_words.p + woff[gr.W1 - 1], jb.m, gr.rows, cs);
+            int rc = ss_counter_insert_words(gr.table, g->cls_words.p + p.woff[gr.W1 - 1], jb.m, gr.rows, cs);
             if (!rc) rc = ss_counter_overflow(gr.table, g->ovf.p + j, cs);
-            if (rc) break;
-            const uint64_t* sel = dense_L ? nullptr : g->order.p + jb.start;
-            hipLaunchKernelGGL(k_rowmap, dim3(grid_of(jb.m, 256)), dim3(256), 0, cs, sel, jb.m, base,
+            if (rc) return rc;
+            hipLaunchKernelGGL(k_rowmap, dim3(grid_of(jb.m, 256)), dim3(256), 0, cs, sel_of(g, c, jb), jb.m, c.base,
                                gr.rowmap.p + gr.rows);
             gr.rows += jb.m;
-        }
-        for (int k = 0; k < used; ++k) {     // join (also after an error: nothing may run on past the call)
-            const int e = ss_check(hipEventRecord(g->ev_join[k], g->side[k]), "ingest join");
-            const int w = e ? e : ss_check(hipStreamWaitEvent(s, g->ev_join[k], 0), "ingest join wait");
-            if (!rc) rc = w;
-        }
-        if (rc) return rc;
+            return rc;
+        });
     }
+    // the classes' rows counted by fingerprint in one scratch table, checked against their
+    // fingerprints' first rows and folded into the class tables (ss_classes_verify_fold); a
+    // fingerprint shared by two keys sends the classes to the exact path (collect_chunk, after the sync)
+    const bool flat = p.flat;
+    uint64_t need_all = flat ? 1 : 0;     // (the zero rows' entry)
+    std::vector<ss_class_rows> cr;
+    ss_flat_class fc[6] = {};
+    for (size_t j : p.cls_jobs) {
+        const Job& jb = p.jobs[j];
+        Group& gr = g->groups[jb.bin];
+        need_all += std::min<uint64_t>(jb.m, p.need_cls[gr.W1 - 1]);
+        if (flat) fc[gr.W1 - 1] = {gr.table, gr.rows, gr.rowmap.p + gr.rows};
+        else cr.push_back({gr.table, g->cls_words.p + p.woff[gr.W1 - 1], jb.m, gr.rows, gr.W1});
+    }
+    // twice the estimate; past 2^24 slots 1.5 times: the per-slot passes (a 64-B representative per
+    // slot, the extract) then cost more than a fuller table's longer probes (2^24-pool batch
+    // 20.8 -> 19.4 ms; at 2^20 the fuller 2^21 table was 0.4 ms slower, libab_f2_lf15_u2{0,4}.log)
+    uint64_t fwant = pow2_at_least(2 * need_all + 2);
+    if (fwant > (1ull << 24)) fwant = pow2_at_least(need_all + need_all / 2 + 2);
+    const uint64_t fcap = std::min<uint64_t>(1ull << 32, std::max<uint64_t>(1ull << 19, fwant));
+    // grow-only with hysteresis: a stream whose per-chunk estimates cross a power of
+    // two keeps its table; only a table 8x too large (its per-slot passes, reps and fold, scale
+    // with the capacity) is replaced by a smaller one
+    if (g->fpt && (ss_counter_capacity(g->fpt) < fcap || ss_counter_capacity(g->fpt) >= 8 * fcap)) {
+        (void)hipStreamSynchronize(s);
+        ss_counter_destroy(g->fpt);
+        g->fpt = nullptr;
+    }
+    if (!g->fpt && (rc = ss_counter_create(fcap, &g->fpt))) return rc;
+    // the scratch table's reset with the class tables' queued ones, one dispatch
+    if ((rc = queue_reset(g, g->fpt)) || (rc = flush_prep(g)) || (rc = g->cls_flag.ensure(1))) return rc;
+    // (sizing modes 3 / 4, test hooks: the flag starts raised, as if two keys shared a fingerprint;
+    // 4 keeps the deferred fold and the speculative finish, so the flag is found after they were queued)
+    rc = ss_check(hipMemsetAsync(g->cls_flag.p, g->sizing == 3 || g->sizing == 4 ? 1 : 0, 4, s), "ingest class flag reset");
+    if (!rc) rc = ss_counter_insert_keys(g->fpt, g->cls_fps.p, flat ? c.n : p.cls_rows, 0, s);
+    if (!rc && !flat) rc = ss_classes_verify_fold(g->fpt, g->cls_fps.p, cr.data(), (uint32_t)cr.size(), g->cls_flag.p, s);
+    // the fold is deferred when every class of the chunk starts from an empty table (see pend)
+    bool defer = flat && (g->sizing == 0 || g->sizing >= 4);
+    for (uint32_t W = 2; W < 6; ++W) defer &= !fc[W].table || fc[W].base == 0;
+    if (!rc && flat && defer) {
+        // a first chunk of an add_device / add_blob also queues the speculative finish beside the verify
+        const bool spec = c.spec_ok && c.base == 0 && g->bad_index == kNoSlot;
+        rc = ss_classes_flat_verify(g->fpt, g->cls_words.p, p.w1max, c.n, g->cls_fps.p, g->cls_flag.p, s,
+                                    spec ? (void*)g->ev_reps : nullptr);
+        if (!rc) {      // pending once the flag comes back clear (checked after the chunk's sync)
+            g->pend_S = p.w1max;
+            g->pend_base = c.base;
+            for (uint32_t W = 0; W < 6; ++W) g->pend_fc[W] = fc[W];
+        }
+        if (!rc && spec) rc = spec_launch(g, p.need_cls, c.base + c.n);
+    } else if (!rc && flat) {
+        rc = ss_classes_flat_verify_fold(g->fpt, g->cls_words.p, p.w1max, c.n, g->cls_fps.p, fc, c.base, g->cls_flag.p, s);
+    }
+    p.pend_now = !rc && flat && defer;
+    if (!rc) rc = ss_counter_overflow(g->fpt, g->ovf.p + nj, s);
+    for (size_t q = 0; q < p.cls_jobs.size() && !rc; ++q) {
+        const size_t j = p.cls_jobs[q];
+        Group& gr = g->groups[p.jobs[j].bin];
+        p.cls_base[j] = gr.rows;
+        rc = ss_counter_overflow(gr.table, g->ovf.p + j, s);
+        gr.rows += p.jobs[j].m;        // (their row map: written by the encode, or by the fold for new keys)
+    }
+    return rc;
+}
+
+// Phase 7: the first-bad words, the tables' overflow words (the scratch table's last) and the class fingerprint
+// flag back in one sync; the classes counted again exactly when the flag is raised; the first rejected read
+int collect_chunk(ss_ingest* g, const Chunk& c, ChunkPlan& p) {
+    hipStream_t s = g->stream;
+    const std::vector<Job>& jobs = p.jobs;
+    const size_t nj = jobs.size();
     if (jobs.empty()) {
-        g->nreads += n;
+        g->nreads += c.n;
         return SS_OK;
     }
-    // first-bad words, the class tables' overflow words (the scratch table's last) and the class
-    // fingerprint flag back in one sync
     // (hb: the kLenBins + 1 first-bad words, then ho: the nj + 1 overflow words and the flag)
     uint64_t* hb = g->h_bad;
     uint64_t* ho = hb + kLenBins + 1;
-    rc = ss_check(hipMemcpyAsync(hb, g->first_bad.p, (kLenBins + 1) * 8, hipMemcpyDeviceToHost, s), "ingest bad copy");
+    int rc = ss_check(hipMemcpyAsync(hb, g->first_bad.p, (kLenBins + 1) * 8, hipMemcpyDeviceToHost, s), "ingest bad copy");
     if (!rc) rc = ss_check(hipMemcpyAsync(ho, g->ovf.p, (nj + 1) * 8, hipMemcpyDeviceToHost, s), "ingest overflow copy");
-    if (!rc && fused && !cls_jobs.empty())
+    if (!rc && p.by_fp())
         rc = ss_check(hipMemcpyAsync(ho + nj + 1, g->cls_flag.p, 4, hipMemcpyDeviceToHost, s), "ingest flag copy");
     if (!rc) rc = ss_check(hipStreamSynchronize(s), "ingest chunk");
     if (rc) return rc;
-    for (size_t j = 0; j <= nj; ++j) {
-        if (!ho[j] || (j == nj && !(fused && !cls_jobs.empty()))) continue;
-        g->failed = true;
-        return ss_fail(SS_EFULL, "ingest: a length class's table ran full (its distinct-key estimate was low); "
-                                     "count again with ss_ingest_set_exact");
-    }
-    g->pend = pend_now && !(uint32_t)ho[nj + 1];
-    if (fused && !cls_jobs.empty() && (uint32_t)ho[nj + 1]) {
+    for (size_t j = 0; j <= nj; ++j)
+        if (ho[j] && (j < nj || p.by_fp())) return fail_full(g, true);
+    g->pend = p.pend_now && !(uint32_t)ho[nj + 1];
+    if (p.by_fp() && (uint32_t)ho[nj + 1]) {
         spec_wait(g);                  // (it reads the class tables the exact path now fills)
         // two keys share a fingerprint: the class tables were left untouched, count them exactly
-        if (flat) {     // class-ordered rows and their row maps first (the one-pass class encode)
+        if (p.flat) {   // class-ordered rows and their row maps first (the one-pass class encode)
             uint64_t* cmap[33] = {nullptr};
-            for (size_t j : cls_jobs) {
+            for (size_t j : p.cls_jobs) {
                 Group& gr = g->groups[jobs[j].bin];
-                cmap[gr.W1 - 1] = gr.rowmap.p + cls_base[j];
+                cmap[gr.W1 - 1] = gr.rowmap.p + p.cls_base[j];
             }
-            rc = ss_encode_classes_impl(d_buf, d_offs, d_lens, n, g->blkhist.p, kSplitBlocks, woff, fpoff, cmap, base,
-                                        kClassBin0, w1max, g->cls_words.p, g->cls_fps.p, g->hll.p, g->first_bad.p + kLenBins, s);
+            rc = ss_encode_classes_impl(c.d_buf, c.d_offs, c.d_lens, c.n, g->blkhist.p, kSplitBlocks, p.woff, p.fpoff, cmap,
+                                        c.base, kClassBin0, p.w1max, g->cls_words.p, g->cls_fps.p, g->hll.p,
+                                        g->first_bad.p + kLenBins, s);
             if (rc) return rc;
         }
-        for (size_t j : cls_jobs) {
+        for (size_t j : p.cls_jobs) {
             Group& gr = g->groups[jobs[j].bin];
-            if ((rc = ss_counter_insert_words(gr.table, g->cls_words.p + woff[gr.W1 - 1], jobs[j].m, cls_base[j], s)) ||
+            if ((rc = ss_counter_insert_words(gr.table, g->cls_words.p + p.woff[gr.W1 - 1], jobs[j].m, p.cls_base[j], s)) ||
                 (rc = ss_counter_overflow(gr.table, g->ovf.p + j, s)))
                 return rc;
         }
@@ -1719,49 +1738,66 @@ int process_chunk(ss_ingest* g, const uint8_t* d_buf, const uint64_t* d_offs, co
         if (!rc) rc = ss_check(hipStreamSynchronize(s), "ingest exact classes");
         if (rc) return rc;
         for (size_t j = 0; j < nj; ++j)
-            if (ho[j]) {
-                g->failed = true;
-                return ss_fail(SS_EFULL, "ingest: a length class's table ran full; count again with ss_ingest_set_exact");
-            }
+            if (ho[j]) return fail_full(g, false);
     }
     for (size_t j = 0; j <= nj; ++j) {
         const uint64_t fb = hb[j < nj ? jobs[j].bin : kLenBins];
-        if (fb == kNoSlot || (j < nj && base + jobs[j].first > g->bad_index)) continue;
+        if (fb == kNoSlot || (j < nj && c.base + jobs[j].first > g->bad_index)) continue;
         // a length's insert reports its row (rows are in read order); the class encodes and the short
         // group's keys report the read
-        const bool by_row = j < nj && !dense_L && jobs[j].bin <= 32 && jobs[j].bin != kShortBin;
+        const bool by_row = j < nj && !c.dense_L && jobs[j].bin <= 32 && jobs[j].bin != kShortBin;
         uint64_t idx = fb;
-        if (by_row) {
-            rc = ss_check(hipMemcpy(&idx, g->order.p + jobs[j].start + fb, 8, hipMemcpyDeviceToHost), "ingest bad row");
-            if (rc) return rc;
-        }
-        if (base + idx < g->bad_index) {
-            g->bad_index = base + idx;
+        if (by_row && (rc = ss_check(hipMemcpy(&idx, g->order.p + jobs[j].start + fb, 8, hipMemcpyDeviceToHost), "ingest bad row")))
+            return rc;
+        if (c.base + idx < g->bad_index) {
+            g->bad_index = c.base + idx;
             g->bad_kind = SS_EINVALID_BASE;
-            uint32_t L = dense_L ? dense_L : (by_row ? jobs[j].bin : 0u);
-            if (!L && (rc = ss_check(hipMemcpy(&L, d_lens + idx, 4, hipMemcpyDeviceToHost), "ingest bad len")))
+            uint32_t L = c.dense_L ? c.dense_L : (by_row ? jobs[j].bin : 0u);
+            if (!L && (rc = ss_check(hipMemcpy(&L, c.d_lens + idx, 4, hipMemcpyDeviceToHost), "ingest bad len")))
                 return rc;
-            uint64_t off = dense_L ? idx * dense_L : 0;
-            if (h_offs) {
-                off = (*h_offs)[idx];
-            } else if (!dense_L &&
-                       (rc = ss_check(hipMemcpy(&off, d_offs + idx, 8, hipMemcpyDeviceToHost), "ingest bad off"))) {
+            uint64_t off = c.h_offs ? (*c.h_offs)[idx] : idx * c.dense_L;
+            if (!c.h_offs && !c.dense_L && (rc = ss_check(hipMemcpy(&off, c.d_offs + idx, 8, hipMemcpyDeviceToHost), "ingest bad off")))
                 return rc;
-            }
-            if (h_chunk) {
-                g->bad_bytes.assign((const char*)h_chunk + off, L);
+            if (c.h_chunk) {
+                g->bad_bytes.assign((const char*)c.h_chunk + off, L);
             } else {
                 g->bad_bytes.assign(L, '\0');
-                rc = ss_check(hipMemcpy(&g->bad_bytes[0], d_buf + off, L, hipMemcpyDeviceToHost), "ingest bad read");
+                rc = ss_check(hipMemcpy(&g->bad_bytes[0], c.d_buf + off, L, hipMemcpyDeviceToHost), "ingest bad read");
                 if (rc) return rc;
             }
         }
     }
     // a too-long read's bytes (the message does not quote them) are not needed
-    g->nreads += n;
+    g->nreads += c.n;
     // the queued finish stands for this count unless a read was rejected (the finish is then not asked for)
     g->spec_valid = g->spec_inflight && g->pend && g->bad_index == kNoSlot;
     return SS_OK;
+}
+
+// One chunk counted: the entry checks, then the phases above in order
+int process_chunk(ss_ingest* g, Chunk c) {
+    spec_wait(g);                    // (its buffers are reused below; the results change)
+    if (g->failed) return fail_earlier();
+    if (c.n == 0) return SS_OK;
+    if (c.n >= (1ull << 32)) return ss_fail(SS_EARG, "ingest: a chunk holds < 2^32 reads");
+    int rc = flush_pending(g);       // the previous chunk's deferred fold (its scratch is reused below)
+    if (rc) return rc;
+    if (g->since_spill + c.n > g->spill_limit && (rc = spill_counts(g))) return rc;
+    g->since_spill += c.n;
+    // global read indices are u64 (row maps); a table's first index is a row of its group, u32: a
+    // group about to pass kMaxRows rows is re-keyed first (group_room)
+    c.base = g->nreads;
+    ChunkPlan p;
+    if ((rc = split_chunk(g, c, p)) || (rc = plan_classes(g, c, p)) || (rc = encode_classes(g, c, p))) return rc;
+    // new groups' pooled tables: their resets are queued (table_get) and set in one dispatch before the
+    // first insert (flush_prep); whatever an early exit leaves queued goes out here
+    g->defer_prep = true;
+    rc = size_tables(g, c, p);
+    if (!rc) rc = insert_fixed(g, c, p);
+    if (!rc) rc = count_classes(g, c, p);
+    g->defer_prep = false;
+    if (!g->prep_p.empty()) (void)flush_prep(g);
+    return rc ? rc : collect_chunk(g, c, p);
 }
 
 // Every table of the engine extracted (entries of group q into its fps / words / counts / first /
@@ -2022,7 +2058,7 @@ int ss_ingest_add_blob(ss_ingest* g, const uint8_t* h_blob, const uint32_t* h_le
         rc = ss_check(hipMemcpyAsync(g->offs.p, offs.data(), n * 8, hipMemcpyHostToDevice, s), "ingest H2D");
         if (!rc) rc = ss_check(hipMemcpyAsync(g->dlens.p, h_lens, n * 4, hipMemcpyHostToDevice, s), "ingest H2D");
     }
-    if (!rc) rc = process_chunk(g, g->dbuf.p, g->offs.p, g->dlens.p, total, n, dense, &offs, h_blob, true);
+    if (!rc) rc = process_chunk(g, {g->dbuf.p, g->offs.p, g->dlens.p, total, n, dense, &offs, h_blob, true});
     if (!rc) rc = ss_check(hipStreamSynchronize(s), "ingest blob");   // staging reusable after return
     return rc;
 }
@@ -2032,7 +2068,7 @@ int ss_ingest_add_device(ss_ingest* g, const uint8_t* d_blob, uint64_t nbytes, c
     if (!g || (n && (!d_blob || !d_offsets || !d_lens))) return ss_fail(SS_EARG, "null argument");
     if (n == 0 || g->bad_index != kNoSlot) return SS_OK;
     (void)hipSetDevice(g->device);
-    int rc = process_chunk(g, d_blob, d_offsets, d_lens, nbytes, n, 0, nullptr, nullptr, true);
+    int rc = process_chunk(g, {d_blob, d_offsets, d_lens, nbytes, n, 0, nullptr, nullptr, true});
     if (!rc) rc = ss_check(hipStreamSynchronize(g->stream), "ingest device blob");
     return rc;
 }
@@ -2302,7 +2338,7 @@ int ss_ingest_add_fastq_range(ss_ingest* g, const char* path, uint64_t begin, ui
         }
         if (!at_eof && g->est_scale == 1.0 && use) g->est_scale = (double)(size - begin) / (double)use;
         const auto tc = Clock::now();
-        rc = process_chunk(g, sl.d.p, g->offs.p, g->dlens.p, use, nrec, 0, nullptr, sl.h.p);
+        rc = process_chunk(g, {sl.d.p, g->offs.p, g->dlens.p, use, nrec, 0, nullptr, sl.h.p});
         g->fq_ms[3] += since(tc);
         if (rc) break;
         line0 += nl;
@@ -2359,7 +2395,7 @@ int ss_ingest_fastq_stages(ss_ingest* g, double* h_ms, uint64_t* h_h2d_bytes) {
 
 static int finish_impl(ss_ingest* g, uint64_t* h_nkeys, uint64_t* h_nwords) {
     if (!g || !h_nkeys || !h_nwords) return ss_fail(SS_EARG, "null argument");
-    if (g->failed) return ss_fail(SS_EFULL, "ingest: an earlier add ran a table full; reset and count again");
+    if (g->failed) return fail_earlier();
     (void)hipSetDevice(g->device);
     hipStream_t s = g->stream;
     const uint64_t N = g->nreads;
@@ -2382,21 +2418,9 @@ static int finish_impl(ss_ingest* g, uint64_t* h_nkeys, uint64_t* h_nwords) {
     const uint64_t NB = (N + 63) / 64;      // read-map words
     if ((rc = g->slot.ensure(NB))) return rc;
     rc = ss_check(hipMemsetAsync(g->slot.p, 0, NB * 8, s), "ingest read map reset");
-    unsigned long long* bits = (unsigned long long*)g->slot.p;
-    std::vector<GDesc> desc;
     std::vector<Group*> placed;
     // a deferred fold's classes come straight from the scratch (they stay pending: a later add folds them)
     if ((rc = extract_groups(g, placed, g->pend))) return rc;
-    for (size_t q = 0; q < placed.size(); ++q) {
-        Group& gr = *placed[q];
-        hipLaunchKernelGGL(k_mark, dim3(grid_of(gr.m + 1, 256)), dim3(256), 0, s, gr.first.p, gr.m, gr.rowmap.p,
-                           kNoSlot, bits);
-        desc.push_back({gr.words.p, gr.counts.p, gr.W1, gr.L});
-    }
-    const uint64_t empty_at = g->empty_count ? g->empty_first : kNoSlot;
-    if (g->empty_count)
-        hipLaunchKernelGGL(k_mark, dim3(1), dim3(256), 0, s, (const uint64_t*)nullptr, (uint64_t)0,
-                           (const uint64_t*)nullptr, empty_at, bits);
     // the entry and word totals came back with the extraction's sync: no sync until the results
     uint64_t K = g->empty_count ? 1 : 0, NW = 0;
     for (Group* gr : placed) {
@@ -2406,39 +2430,14 @@ static int finish_impl(ss_ingest* g, uint64_t* h_nkeys, uint64_t* h_nwords) {
     // results -> pinned host (results_layout: lens | counts | words), written by the gather
     uint64_t co = 0, wo0 = 0;
     results_layout(K, 0, 8, co, wo0);      // (the plain layout bounds the compact one)
-    if ((rc = g->gdesc.ensure(desc.size() + 1)) || (rc = g->ordered.ensure(K + 1)) ||
+    if ((rc = g->gdesc.ensure(placed.size() + 1)) || (rc = g->ordered.ensure(K + 1)) ||
         (rc = g->woff.ensure(std::max(K, NB) + 1)) || (rc = g->out_host.ensure(wo0 + NW * 8 + 16)) ||
         (rc = g->spec_dev.ensure(13)))
         return rc;
-
-    if (!desc.empty())
-        rc = ss_check(hipMemcpyAsync(g->gdesc.p, desc.data(), desc.size() * sizeof(GDesc), hipMemcpyHostToDevice, s),
-                      "ingest desc");
-    if (rc) return rc;
-    // marked reads before each read-map word (read order = dict order); woff holds that prefix first
-    // (it becomes the word offsets below)
-    hipLaunchKernelGGL((k_scan_count<0>), dim3(kScanBlocks), dim3(256), 0, s, g->slot.p, NB, (const GDesc*)g->gdesc.p,
-                       g->scan.p);
-    hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(256), 0, s, g->scan.p);
-    hipLaunchKernelGGL((k_scan_apply<0>), dim3(kScanBlocks), dim3(256), 0, s, g->slot.p, NB, (const GDesc*)g->gdesc.p,
-                       g->scan.p, g->woff.p);
-    for (size_t q = 0; q < placed.size(); ++q)
-        hipLaunchKernelGGL(k_rank, dim3(grid_of(placed[q]->m + 1, 256)), dim3(256), 0, s, placed[q]->first.p,
-                           placed[q]->m, placed[q]->rowmap.p, (uint32_t)q, kNoSlot, bits, g->woff.p, g->ordered.p);
-    if (g->empty_count)
-        hipLaunchKernelGGL(k_rank, dim3(1), dim3(256), 0, s, (const uint64_t*)nullptr, (uint64_t)0,
-                           (const uint64_t*)nullptr, 0u, empty_at, bits, g->woff.p, g->ordered.p);
-    // word offsets of the ordered entries
-    hipLaunchKernelGGL((k_scan_count<1>), dim3(kScanBlocks), dim3(256), 0, s, g->ordered.p, K, (const GDesc*)g->gdesc.p,
-                       g->scan.p);
-    hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(256), 0, s, g->scan.p);
-    hipLaunchKernelGGL((k_scan_apply<1>), dim3(kScanBlocks), dim3(256), 0, s, g->ordered.p, K, (const GDesc*)g->gdesc.p,
-                       g->scan.p, g->woff.p);
-    if (K >= (1ull << 31) * 256) return ss_fail(SS_EARG, "ingest: too many distinct keys for one gather");
+    std::vector<GDesc> desc(placed.size());
     g->wide = results_wide(g);
-    OutLayout ol{g->out_host.p, g->out_host.cap, nullptr, nullptr, NW, nullptr, g->compact, g->wide ? 1 : 0};
-    hipLaunchKernelGGL(k_gather_host, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, s, g->ordered.p, K,
-                       (const GDesc*)g->gdesc.p, g->woff.p, g->empty_count, ol);
+    const OutLayout ol{g->out_host.p, g->out_host.cap, nullptr, nullptr, NW, nullptr, g->compact, g->wide ? 1 : 0};
+    if ((rc = queue_order(g, s, placed, desc.data(), nullptr, NB, K, ol))) return rc;
     rc = ss_check(hipGetLastError(), "k_gather_host");
     if (!rc) rc = ss_check(hipStreamSynchronize(s), "ingest out");
     if (rc) return rc;
@@ -2451,7 +2450,7 @@ static int finish_impl(ss_ingest* g, uint64_t* h_nkeys, uint64_t* h_nwords) {
 
 int ss_ingest_export(ss_ingest* g, uint64_t* h_nkeys) {
     if (!g) return ss_fail(SS_EARG, "null ingest");
-    if (g->failed) return ss_fail(SS_EFULL, "ingest: an earlier add ran a table full; reset and count again");
+    if (g->failed) return fail_earlier();
     (void)hipSetDevice(g->device);
     std::vector<Group*> placed;
     spec_wait(g);
@@ -2486,7 +2485,7 @@ int ss_ingest_export(ss_ingest* g, uint64_t* h_nkeys) {
 
 int ss_ingest_reserve_merge(ss_ingest* dst, ss_ingest* const* srcs, uint32_t nsrc) {
     if (!dst || (nsrc && !srcs)) return ss_fail(SS_EARG, "ingest reserve merge: null argument");
-    if (dst->failed) return ss_fail(SS_EFULL, "ingest: an earlier add ran a table full; reset and count again");
+    if (dst->failed) return fail_earlier();
     std::map<uint32_t, std::pair<uint64_t, const Group*>> total;      // bin -> (entries, a source group)
     for (uint32_t k = 0; k < nsrc; ++k) {
         ss_ingest* src = srcs[k];
@@ -2523,7 +2522,7 @@ int ss_ingest_reserve_merge(ss_ingest* dst, ss_ingest* const* srcs, uint32_t nsr
 int ss_ingest_merge(ss_ingest* dst, ss_ingest* src, uint64_t src_base) {
     if (!dst || !src || dst == src) return ss_fail(SS_EARG, "ingest merge: two distinct engines");
     if (!src->exported) return ss_fail(SS_EARG, "ingest merge: ss_ingest_export the source first");
-    if (dst->failed) return ss_fail(SS_EFULL, "ingest: an earlier add ran a table full; reset and count again");
+    if (dst->failed) return fail_earlier();
     if (src_base < dst->nreads) return ss_fail(SS_EARG, "ingest merge: sources follow the destination's reads, in order");
     spec_wait(dst);
     spec_wait(src);

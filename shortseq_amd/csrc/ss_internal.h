@@ -17,13 +17,6 @@ int ss_check(hipError_t e, const char* what);
 extern "C" int ss_encode_fixed_impl(const uint8_t* d_ascii, uint64_t n, uint32_t L, uint64_t stride,
                                     uint64_t* d_words, uint32_t wpr, uint64_t* d_first_bad,
                                     const uint64_t* d_ref_words, uint32_t* d_out, void* stream);
-// All multi-word classes of a chunk in one read-order pass (k_encode_classes; every class present has
-// W + 1 <= w1max <= 16 words), over k_len_count's nblk block ranges: class W's rows at d_out + h_woff[W]
-// (W = 2..32; the block's first row of class W = d_blkoff[(bin0 + W) * nblk + block], k_len_binscan's
-// in-bin offsets; rows in read order), each row's fingerprint (words_fp over its W + 1 words) at
-// d_fps[h_fpoff[W] + row] when d_fps is given, its global read index (base + chunk read) at
-// h_rmap[W][row] when h_rmap[W] is given, and the classes' HyperLogLog registers d_hll[W << kHllLog
-// ...] (u32, max-updated; zeroed by the caller).
 constexpr uint32_t kHllLog = 11;
 // ss_counter_reset in two halves: the host state now, its three device words (p[0..2] = v[0..2])
 // queued later, several tables' words in one ss_prep_words dispatch (n <= kPrepMany), before any use
@@ -31,6 +24,13 @@ constexpr uint32_t kHllLog = 11;
 constexpr uint32_t kPrepMany = 32;
 extern "C" int ss_counter_reset_host(ss_counter* c, unsigned long long** p, unsigned long long* v);
 extern "C" int ss_prep_words(unsigned long long* const* p, const unsigned long long* v, uint32_t n, void* stream);
+// All multi-word classes of a chunk in one read-order pass (k_encode_classes; every class present has
+// W + 1 <= w1max <= 16 words), over k_len_count's nblk block ranges: class W's rows at d_out + h_woff[W]
+// (W = 2..32; the block's first row of class W = d_blkoff[(bin0 + W) * nblk + block], k_len_binscan's
+// in-bin offsets; rows in read order), each row's fingerprint (words_fp over its W + 1 words) at
+// d_fps[h_fpoff[W] + row] when d_fps is given, its global read index (base + chunk read) at
+// h_rmap[W][row] when h_rmap[W] is given, and the classes' HyperLogLog registers d_hll[W << kHllLog
+// ...] (u32, max-updated; zeroed by the caller).
 extern "C" int ss_encode_classes_impl(const uint8_t* d_buf, const uint64_t* d_offs, const uint32_t* d_lens, uint64_t n,
                                       const uint32_t* d_blkoff, uint32_t nblk, const uint64_t* h_woff,
                                       const uint64_t* h_fpoff, uint64_t* const* h_rmap, uint64_t base, uint32_t bin0,
