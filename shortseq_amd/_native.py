@@ -119,6 +119,10 @@ SIGNATURES = [
     ("ss_host_decode", None, [_P, _U64, _P]),
     ("ss_host_hamming", _U64, [_P, _P, _U64]),
 ]
+# exported, but declared in csrc/ss_internal.h, not in the public header (test hooks)
+INTERNAL_SIGNATURES = [
+    ("ss_counter_last_route", C.c_int, [_P]),
+]
 
 _lib = None
 
@@ -133,7 +137,7 @@ def lib():
         L = C.CDLL(LIB)
         # A/B runs of an older library build (scripts/gpu.sh libab) may lack symbols added since
         lenient = os.environ.get("SHORTSEQ_AMD_LENIENT_ABI") == "1"
-        for name, res, args in SIGNATURES:
+        for name, res, args in SIGNATURES + INTERNAL_SIGNATURES:
             if lenient and not hasattr(L, name):
                 continue
             f = getattr(L, name)

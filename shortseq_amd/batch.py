@@ -792,6 +792,24 @@ class GpuCounter:
         if check_errors:
             _check_first_bad(fb, _fetch_row(ascii, stride, L))
 
+    ROUTES = ("optimistic", "exact", "exact multi-word", "direct g16", "direct generic")
+
+    def last_route(self) -> Optional[str]:
+        """The kernel chain the last insert took (ss_counter_last_route; None before any insert), for
+        tests that pin the dispatch: the route, then its sub-choices -- "optimistic g16 slabs",
+        "exact k_pc_hist two passes", "exact multi-word one pass", "direct generic", ..."""
+        code = int(lib().ss_counter_last_route(self._h))
+        if code < 0:
+            return None
+        route = self.ROUTES[code & 7]
+        if route == "optimistic":
+            coarse = ("plain", "g16", "keys")[(code >> 5) & 3]
+            return f"optimistic {coarse} {'slabs' if code & 128 else 'counted cursors'}"
+        if route.startswith("exact"):
+            hist = "" if "multi" in route else (" k_pc_keys" if code & 16 else " k_pc_hist")
+            return f"{route}{hist} {'two passes' if code & 8 else 'one pass'}"
+        return route
+
     def _drop_reservation(self) -> None:
         torch.cuda.synchronize(self.device)
         check(lib().ss_counter_release(self._h), "ss_counter_release")

@@ -48,6 +48,42 @@ constexpr uint32_t kMaxRegions = 32768;    // per-block region histogram in LDS 
 
 constexpr int32_t kWordKeys = -2;
 
+// Workspace of the partitioned insert, in two lifetimes: `batch` is sized for a reservation of
+// `reads` reads (ss_counter_reserve allocates it, ss_counter_release frees it), `kept` depends on the
+// table geometry alone and stays until ss_counter_destroy.  ws_bufs() below lists every buffer once,
+// with the bytes a reservation gives it; sizes here are in elements, with
+//   acap  = max(kNFill * cap1, reads)   coarse record slots
+//   brecs = fine record slots: reads, or with slabs 2 x reads + the slabs' slack
+struct InsertWs {
+    uint64_t reads = 0;                    // reads the reservation holds (0: none)
+    uint64_t cap1 = 0;                     // optimistic coarse partition: akey holds 128 x 8 sub-bins of cap1 records
+    uint64_t slab = 0;                     // 1 = fine-scatter slabs per (sub-bin, region), 0 = counted cursors
+    uint64_t brecs = 0;
+    uint64_t words_cap = 0;                // words allocated at batch.words
+    struct Batch {
+        uint64_t* keys = nullptr;          // [brecs] Rec12: the optimistic route's region-ordered records; the exact
+                                           // routes use it as [reads] u64: key of read i, later bucketed by region
+        uint64_t* akey = nullptr;          // [acap] Rec12: the optimistic route's coarse records; the exact routes
+                                           // use it as [reads] u64 keys bucketed by coarse bin
+        uint32_t* aidx = nullptr;          // [reads] exact routes: batch-local read index, coarse order
+        uint32_t* acnt = nullptr;          // [acap] weighted records' counts, coarse order
+        uint8_t* areg = nullptr;           // [acap] region-in-bin byte per coarse record; null with slabs
+        uint32_t* bidx = nullptr;          // [reads] exact routes: batch-local read index, region order
+        uint32_t* bcnt = nullptr;          // [brecs] weighted records' counts, region order
+        uint4* spill = nullptr;            // [reads] records past a full sub-bin or slab
+        uint64_t* words = nullptr;         // [words_cap] multi-word ASCII inserts: the packed reads (reads x W,
+                                           // allocated by the first such insert, not by the reservation)
+    } batch;
+    struct Kept {
+        uint32_t* hist = nullptr;          // [kPartBlocks * regions] per-(block, bin) counts -> offsets
+        uint32_t* rstart = nullptr;        // [regions + 1] region start in the bucket arrays
+        uint32_t* order = nullptr;         // [3 kNFill] sub-bins by descending fill, slab bases, slab sizes (k_pf_order)
+        uint32_t* segend = nullptr;        // [regions x kFinePerBin] end of each (sub-bin, region) fine segment
+        uint32_t* tot = nullptr;           // [regions + 1] scratch (bin totals / coarse starts)
+        uint32_t* fill = nullptr;          // [kFillWords] sub-bin fill counters (fill_at) + the spill counter
+    } kept;
+};
+
 struct ss_counter {
     uint64_t cap = 0;
     uint32_t log2cap = 0;
@@ -57,30 +93,10 @@ struct ss_counter {
     uint32_t W = 1;                        // words per key: 1 (L <= 32) or ceil(L/32) (multi-word keys)
     Slot* slots = nullptr;                 // [cap + 1]; multi-word: slot.key = 64-bit fingerprint
     uint64_t* keywords = nullptr;          // multi-word keys: [cap * W] the key words of slot s
-    uint64_t* ws_words = nullptr;          // multi-word insert workspace: [ws_words_cap] packed reads
-    uint64_t ws_words_cap = 0;             // words allocated at ws_words
     uint32_t keywords_W = 0;               // W the keywords array was allocated for
     unsigned long long* work = nullptr;    // [0]: overflow flags, [1..]: per-(part, block) counts
-    // partitioned-insert workspace (ss_counter_reserve)
-    uint64_t ws_reads = 0;
-    uint64_t* ws_keys = nullptr;           // [ws_reads] packed key of read i; later bucketed by region
-    uint64_t* ws_akey = nullptr;           // [ws_reads] keys bucketed by coarse bin
-    uint32_t* ws_aidx = nullptr;           // [ws_reads] batch-local read index, same order
-    uint32_t* ws_acnt = nullptr;           // weighted records' counts, coarse order (same size as ws_aidx)
-    uint8_t* ws_areg = nullptr;            // region-in-bin byte per coarse record (same size as ws_aidx)
-    uint32_t* ws_bidx = nullptr;           // [ws_reads] batch-local read index, region order
-    uint32_t* ws_bcnt = nullptr;           // [ws_reads] weighted records' counts, region order
-    uint4* ws_spill = nullptr;             // [ws_reads] records past a full sub-bin
-    uint32_t* ws_hist = nullptr;           // [kPartBlocks * regions] per-(block, bin) counts -> offsets
-    uint32_t* ws_rstart = nullptr;         // [regions + 1] region start in the bucket arrays
-    uint32_t* ws_order = nullptr;          // [3 kNFill] sub-bins by descending fill, slab bases, slab sizes (k_pf_order)
-    uint32_t* ws_segend = nullptr;         // [regions x kFinePerBin] end of each (sub-bin, region) fine segment
-    uint32_t* ws_tot = nullptr;            // [regions + 1] scratch (bin totals / coarse starts)
-    // optimistic coarse partition (k_pf_coarse): ws_akey / ws_aidx hold 128 bins of ws_cap1 slots
-    uint64_t ws_cap1 = 0;
-    uint64_t ws_slab = 0;                  // 1 = fine-scatter slabs per (sub-bin, region), 0 = counted cursors
-    uint64_t ws_brecs = 0;                 // fine-record slots (ws_keys / ws_bidx / ws_bcnt)
-    uint32_t* ws_fill = nullptr;           // sub-bin fill counters + the spill counter, kFillStride apart
+    InsertWs ws;                           // partitioned-insert workspace (ss_counter_reserve)
+    int last_route = -1;                   // Route of the last insert (ss_counter_last_route), -1: none yet
     // per-region occupancy (used slots of each slice), written by the single-word aggregate (and
     // kept by the spill insert); lets ss_counter_pack_ranges skip its counting pass.
     // occ_src: 0 = stale, 1 = valid
@@ -2193,7 +2209,7 @@ __global__ __launch_bounds__(kPackT) void k_region_pack(Tbl t, uint32_t R, uint3
 // ------------------------------------------------------------------------------------------------
 // Multi-word keys (33..1024 nt: W = ceil(L/32) words; ShortSeq192 / ShortSeqVar keys,
 // short_seq_192.pyx:35-41 / short_seq_var.pyx:22-28: equal iff length and all words equal).
-// The reads are packed first (ss_encode_fixed into ws_words), keyed by a 64-bit fingerprint of
+// The reads are packed first (ss_encode_fixed into ws.batch.words), keyed by a 64-bit fingerprint of
 // their words, and go through the same partition passes.  Equality is always decided on the full
 // words: the LDS table claims a slot with ONE 64-bit CAS of (fingerprint high half | representative
 // read index), so a thread that meets a claimed slot can compare words immediately (no waiting on
@@ -2652,6 +2668,197 @@ int launch_merge(ss_counter* c, Recs recs, const uint64_t* d_run_offsets, uint32
     }
     hipLaunchKernelGGL((k_merge_sentinel<Recs>), dim3(1), dim3(64), 0, s, t, recs, d_run_offsets, n_runs);
     return ss_check(hipGetLastError(), what);
+}
+
+// ---- insert workspace ------------------------------------------------------------------------------
+// Every buffer of InsertWs, once: the first kWsBatch belong to the reservation, the rest to the
+// handle.  bytes = what a reservation of `reads` reads over R regions allocates for the buffer, from
+// w.cap1 / w.slab / w.brecs (0: the reservation does not allocate it).  ss_counter_reserve allocates
+// the null ones, ss_counter_release frees the first kWsBatch, ss_counter_destroy the rest.
+struct WsBuf {
+    void** slot;
+    size_t bytes;
+};
+constexpr int kWsBatch = 9, kWsBufs = 15;
+struct WsBufs {
+    WsBuf b[kWsBufs];
+};
+WsBufs ws_bufs(InsertWs& w, uint64_t reads, uint64_t R) {
+    // coarse arrays: room for the exact passes (reads) and for the optimistic partition's 128 x 8
+    // sub-bins of cap1 = 2.5 x the mean sub-bin load + 1024 slots (pf_cap1)
+    const uint64_t acap = kNFill * w.cap1 > reads ? kNFill * w.cap1 : reads;
+    InsertWs::Batch& b = w.batch;
+    InsertWs::Kept& k = w.kept;
+    return {{
+        {(void**)&b.keys, w.brecs * sizeof(Rec12)},
+        {(void**)&b.akey, acap * sizeof(Rec12)},
+        {(void**)&b.aidx, reads * sizeof(uint32_t)},
+        {(void**)&b.acnt, acap * sizeof(uint32_t)},
+        {(void**)&b.areg, w.slab ? 0 : acap},   // counted cursors only
+        {(void**)&b.bidx, reads * sizeof(uint32_t)},
+        {(void**)&b.bcnt, w.brecs * sizeof(uint32_t)},
+        {(void**)&b.spill, reads * sizeof(uint4)},
+        {(void**)&b.words, 0},                  // insert_exact, at the first multi-word ASCII batch
+        {(void**)&k.hist, (size_t)kPartBlocks * R * sizeof(uint32_t)},
+        {(void**)&k.rstart, (R + 1) * sizeof(uint32_t)},
+        {(void**)&k.order, 3 * kNFill * sizeof(uint32_t)},
+        // one entry per (sub-bin, region of its bin): kNFill x (R / 128) = R x kFinePerBin
+        {(void**)&k.segend, R * kFinePerBin * sizeof(uint32_t)},
+        {(void**)&k.tot, (R + 1) * sizeof(uint32_t)},
+        {(void**)&k.fill, kFillWords * sizeof(uint32_t)},
+    }};
+}
+
+void ws_free(const WsBufs& t, int from, int to) {
+    for (int i = from; i < to; ++i) {
+        if (*t.b[i].slot) (void)hipFree(*t.b[i].slot);
+        *t.b[i].slot = nullptr;
+    }
+}
+
+// The workspace as the partition kernels take it.  The fields only one route uses (slab, slabs,
+// spill_ctr, seg_end, bkey, brec) start out null / 0; the route sets them.
+PartWs part_ws(const ss_counter* c) {
+    PartWs w{};
+    w.keys = c->ws.batch.keys;
+    w.akey = c->ws.batch.akey;
+    w.aidx = c->ws.batch.aidx;
+    w.acnt = c->ws.batch.acnt;
+    w.areg = c->ws.batch.areg;
+    w.bidx = c->ws.batch.bidx;
+    w.bcnt = c->ws.batch.bcnt;
+    w.spill = c->ws.batch.spill;
+    w.spill_cap = c->ws.reads;
+    w.hist = c->ws.kept.hist;
+    w.rstart = c->ws.kept.rstart;
+    w.tot = c->ws.kept.tot;
+    w.R = (uint32_t)(c->cap >> c->slice_log);
+    w.rbits = c->log2cap - c->slice_log;
+    return w;
+}
+
+// ---- insert dispatch -------------------------------------------------------------------------------
+// What an insert reads (ss_counter_insert_fixed / _words / _keys build it).
+struct InsertSrc {
+    enum class Kind { Ascii, Words, Keys } kind;
+    struct AsciiRows {
+        const uint8_t* rows;   // [n] reads of L bytes, `stride` bytes apart
+        uint32_t L;
+        uint64_t stride;
+        uint64_t* first_bad;   // device word: min read index with a rejected byte
+    };
+    union {
+        AsciiRows ascii;
+        const uint64_t* words;   // [n][W] packed rows of a ss_counter_set_words handle
+        const uint64_t* keys;    // [n] single-word keys, any 64-bit values
+    };
+};
+
+// The five kernel chains an insert can take (ss_counter_last_route reports the values).
+enum class Route : int {
+    Optimistic = 0,     // k_prep, k_pf_coarse, [k_pf_count + scans], k_pf_order, k_pf_scatter, aggregate<REC12>, k_spill_insert
+    Exact = 1,          // k_pc_keys or encode / copy + k_pc_hist, one or two exact scatters, aggregate
+    ExactMulti = 2,     // multi-word keys: [encode], k_mw_fp, one or two exact scatters, k_mw_aggregate
+    DirectG16 = 3,      // no workspace for the batch: k_count_g16 straight into the table
+    DirectGeneric = 4,  // the same for any other length / layout: k_count_gen
+};
+enum class Coarse : int { Plain = 0, G16 = 1, Keys = 2 };   // the k_pf_coarse<KEYS, G16> instance
+struct InsertPlan {
+    Route route;
+    bool two_pass;    // exact routes: coarse + fine scatter (> 128 regions), else one scatter by region
+    bool hist_keys;   // Exact: keys and histogram by the fused k_pc_keys, else encode / copy + k_pc_hist
+    Coarse coarse;    // Optimistic
+    bool slab;        // Optimistic: fine-scatter slabs, else counted cursors (k_pf_count + scans)
+};
+
+// The fine passes keep a record's region within its coarse bin in a byte.  A workspace exists only
+// for R <= kMaxRegions (ss_counter_reserve), so a batch that fits its reservation needs no test of it.
+static_assert(kMaxRegions <= 1u << (kCoarseBits + 8), "region-in-bin fits a byte");
+
+// The route of n > 0 reads from src into c, and the route's sub-choices: a function of the handle's
+// geometry, key width and reservation, the source's kind and (ASCII) its length, stride and alignment.
+// Key input and multi-word handles grow the reservation to the batch themselves (keys: before this
+// is called; multi-word: insert_exact), so only single-word ASCII batches can fail to fit.
+InsertPlan plan_insert(const ss_counter* c, const InsertSrc& src, uint64_t n) {
+    InsertPlan p{};
+    const bool two_pass = c->log2cap - c->slice_log > kCoarseBits;
+    if (c->W > 1) {
+        p.route = Route::ExactMulti;
+        p.two_pass = two_pass;
+        return p;
+    }
+    const bool keys = src.kind == InsertSrc::Kind::Keys;
+    // 16 / 32-nt rows the kernels can load as aligned dwordx4
+    const bool aligned16 = src.kind == InsertSrc::Kind::Ascii && src.ascii.rows &&
+                           (src.ascii.L == 16 || src.ascii.L == 32) && src.ascii.stride % 16 == 0 &&
+                           (((uintptr_t)src.ascii.rows) & 15) == 0;
+    if (n > c->ws.reads) {
+        p.route = aligned16 ? Route::DirectG16 : Route::DirectGeneric;
+    } else if (two_pass && (keys || aligned16)) {
+        p.route = Route::Optimistic;
+        p.coarse = keys ? Coarse::Keys : src.ascii.L == 32 ? Coarse::G16 : Coarse::Plain;
+        p.slab = c->ws.slab != 0;
+    } else {
+        p.route = Route::Exact;
+        p.two_pass = two_pass;
+        p.hist_keys = aligned16;   // (then one pass: two passes with aligned rows is the optimistic route)
+    }
+    return p;
+}
+
+// ss_counter_last_route's value: the route, then the plan's sub-choices as flag bits
+int route_code(const InsertPlan& p) {
+    return (int)p.route | (p.two_pass ? 8 : 0) | (p.hist_keys ? 16 : 0) | ((int)p.coarse << 5) | (p.slab ? 128 : 0);
+}
+
+// block sizes of the exact routes' kernels
+constexpr int kKeysT = 512, kKeysU = 2, kCountT = 512, kHistT = 512;
+static_assert(kHistT == kMwFpT, "k_mw_fp instances");
+
+// dynamic LDS of a per-block histogram over `bins` bins in blocks of T threads: one copy per wave
+// while those fit, else one per block
+size_t hist_lds_bytes(uint32_t bins, int T) {
+    return (bins * (T / 64) <= kMaxRegions ? bins * (T / 64) : bins) * 4;
+}
+
+// Dynamic LDS above the 64 KB default: the kernels' opt-in, made once per process (a host-side
+// attribute; a function-local static is initialised once even with engines on several threads)
+hipError_t lds_opt_in() {
+    static const hipError_t attrs = [] {
+        const int agg_max = (int)(2 * (1u << kMwSliceLog) * 16 + (1u << kMwSliceLog) * 8 + 8);
+        hipError_t ea = hipFuncSetAttribute((const void*)k_pc_keys<kKeysT, kKeysU>,
+                                            hipFuncAttributeMaxDynamicSharedMemorySize, kMaxRegions * 4);
+        if (ea == hipSuccess)
+            ea = hipFuncSetAttribute((const void*)k_pc_hist<kHistT>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                     kMaxRegions * 4);
+        for (int f = 0; f < kMwAggFns && ea == hipSuccess; ++f)
+            ea = hipFuncSetAttribute((const void*)kMwFp[f], hipFuncAttributeMaxDynamicSharedMemorySize,
+                                     kMaxRegions * 4);
+        for (int f = 0; f < kMwAggFns && ea == hipSuccess; ++f)
+            ea = hipFuncSetAttribute((const void*)kMwAgg[f], hipFuncAttributeMaxDynamicSharedMemorySize, agg_max);
+        return ea;
+    }();
+    return attrs;
+}
+
+// k_pf_coarse's grid: it strides over tiles, so exactly the resident blocks (no second, partial
+// round); queried once per process
+int pf_resident_grid() {
+    static const int grid = [] {
+        int dev = 0, cus = 0, per = 0;
+        (void)hipGetDevice(&dev);
+        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, (const void*)k_pf_coarse<kPfT, kPfRPL, false, true>, kPfT, 0);
+        return (cus > 0 && per > 0) ? cus * per : (int)kPartBlocks;
+    }();
+    return grid;
+}
+
+// per-(block, bin) counts in w.hist -> write offsets, bin starts at `start` (k_pc_tot / k_pc_scan / k_pc_offsets)
+void launch_scan(const PartWs& w, uint32_t bins, uint32_t* start, hipStream_t s) {
+    hipLaunchKernelGGL(k_pc_tot, dim3(bins), dim3(256), 0, s, w, bins);
+    hipLaunchKernelGGL(k_pc_scan, dim3(1), dim3(1024), 0, s, w, bins, start);
+    hipLaunchKernelGGL(k_pc_offsets, dim3(bins), dim3(1024), 0, s, w, bins, (const uint32_t*)start);
 }
 
 }  // namespace
@@ -3337,12 +3544,7 @@ int ss_counter_destroy(ss_counter* c) {
     if (c->roff) (void)hipFree(c->roff);
     if (c->aux) (void)hipFree(c->aux);
     ss_counter_release(c);
-    if (c->ws_hist) (void)hipFree(c->ws_hist);
-    if (c->ws_rstart) (void)hipFree(c->ws_rstart);
-    if (c->ws_segend) (void)hipFree(c->ws_segend);
-    if (c->ws_order) (void)hipFree(c->ws_order);
-    if (c->ws_tot) (void)hipFree(c->ws_tot);
-    if (c->ws_fill) (void)hipFree(c->ws_fill);
+    ws_free(ws_bufs(c->ws, 0, 0), kWsBatch, kWsBufs);
     delete c;
     return SS_OK;
 }
@@ -3424,6 +3626,20 @@ int ss_prep_words(unsigned long long* const* p, const unsigned long long* v, uin
 
 uint64_t ss_counter_capacity(const ss_counter* c) { return c ? c->cap : 0; }
 
+// key words of a multi-word table: [cap * W], kept while W stays the same
+static int alloc_keywords(ss_counter* c, uint32_t W) {
+    if (c->keywords_W == W) return SS_OK;
+    if (c->keywords) (void)hipFree(c->keywords);
+    c->keywords = nullptr;
+    c->keywords_W = 0;
+    if (hipMalloc((void**)&c->keywords, c->cap * W * sizeof(uint64_t)) != hipSuccess) {
+        ss_check(hipGetLastError(), "counter key words hipMalloc");
+        return ss_fail(SS_ENOMEM, "counter key words: out of device memory");
+    }
+    c->keywords_W = W;
+    return SS_OK;
+}
+
 static int fix_length(ss_counter* c, uint32_t L) {
     if (L > SS_MAX_NT) return ss_fail(SS_ETOO_LONG, "Sequences longer than 1024 bases are not supported.");
     if (c->L == kWordKeys) return ss_fail(SS_EARG, "the handle holds packed multi-word keys");
@@ -3432,16 +3648,8 @@ static int fix_length(ss_counter* c, uint32_t L) {
         return SS_OK;
     }
     const uint32_t W = L <= 32 ? 1u : (L + 31) / 32;
-    if (W > 1 && c->keywords_W != W) {   // key words of a multi-word table: [cap * W]
-        if (c->keywords) (void)hipFree(c->keywords);
-        c->keywords = nullptr;
-        c->keywords_W = 0;
-        if (hipMalloc((void**)&c->keywords, c->cap * W * sizeof(uint64_t)) != hipSuccess) {
-            ss_check(hipGetLastError(), "counter key words hipMalloc");
-            return ss_fail(SS_ENOMEM, "counter key words: out of device memory");
-        }
-        c->keywords_W = W;
-    }
+    int rc = SS_OK;
+    if (W > 1 && (rc = alloc_keywords(c, W))) return rc;
     c->W = W;
     c->L = (int32_t)L;
     return SS_OK;
@@ -3452,113 +3660,262 @@ int ss_counter_reserve(ss_counter* c, uint64_t max_reads) {
     const uint64_t R = c->cap >> c->slice_log;
     if (R > kMaxRegions) return ss_fail(SS_EARG, "capacity too large for the partitioned insert");
     if (max_reads >= (1ull << 31)) return ss_fail(SS_EARG, "max_reads must be < 2^31 per insert");
-    if (max_reads <= c->ws_reads) return SS_OK;
+    if (max_reads <= c->ws.reads) return SS_OK;
     ss_counter_release(c);
-    // coarse arrays: room for the exact passes (max_reads) and for the optimistic partition's
-    // 128 x 8 sub-bins of cap1 = 2.5 x the mean sub-bin load + 1024 slots (pf_cap1)
-    const uint64_t cap1 = pf_cap1(max_reads);
-    const uint64_t acap = kNFill * cap1 > max_reads ? kNFill * cap1 : max_reads;
+    InsertWs& ws = c->ws;
+    ws.cap1 = pf_cap1(max_reads);
     // fine-pass slabs (optimistic path, R > 128 regions): every (sub-bin, region of its bin) gets
     // slab_size(sub-bin fill) record slots (2 x its mean share + 256; k_pf_order lays them out once
     // the coarse fills are known), so the fine scatter needs no count pass; a slab that runs full
     // sends the rest to the spill list.  Only where the mean share is >= kSlabMinMean (the per-slab
     // slack would dominate small reservations) and the slots index in 32 bits.
-    c->ws_slab = 0;
-    c->ws_brecs = max_reads;
-    if (R > (1u << kCoarseBits) && R <= (1u << (kCoarseBits + 8))) {
+    ws.slab = 0;
+    ws.brecs = max_reads;
+    if (R > (1u << kCoarseBits)) {
         const uint64_t nslab = (uint64_t)kNFill * (R >> kCoarseBits);
         const uint64_t mean = max_reads / nslab;
         // sum over sub-bins of nb x slab_size(fill, nb), fills summing to <= max_reads
         const uint64_t brecs = 2 * max_reads + nslab * (2 + kSlabPad + 15);
         if (mean >= kSlabMinMean && brecs < (1ull << 32)) {
-            c->ws_slab = 1;
-            c->ws_brecs = brecs > max_reads ? brecs : max_reads;
+            ws.slab = 1;
+            ws.brecs = brecs > max_reads ? brecs : max_reads;
         }
     }
-    const uint64_t brecs = c->ws_brecs;
-    // ws_keys / ws_akey: 12-B records on the optimistic path, u64 keys on the exact paths
-    hipError_t e = hipMalloc((void**)&c->ws_keys, brecs * sizeof(Rec12));
-    if (e == hipSuccess) e = hipMalloc((void**)&c->ws_akey, acap * sizeof(Rec12));
-    // coarse read indices of the exact paths (the optimistic path keeps them in the 12-B records)
-    if (e == hipSuccess) e = hipMalloc((void**)&c->ws_aidx, max_reads * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMalloc((void**)&c->ws_acnt, acap * sizeof(uint32_t));
-    if (e == hipSuccess && !c->ws_slab) e = hipMalloc((void**)&c->ws_areg, acap);   // counted cursors only
-    if (e == hipSuccess && !c->ws_fill) e = hipMalloc((void**)&c->ws_fill, kFillWords * sizeof(uint32_t));
-    c->ws_cap1 = cap1;
-    if (e == hipSuccess) e = hipMalloc((void**)&c->ws_bidx, max_reads * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMalloc((void**)&c->ws_bcnt, brecs * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMalloc((void**)&c->ws_spill, max_reads * sizeof(uint4));
-    if (e == hipSuccess && !c->ws_hist) e = hipMalloc((void**)&c->ws_hist, (size_t)kPartBlocks * R * sizeof(uint32_t));
-    if (e == hipSuccess && !c->ws_rstart) e = hipMalloc((void**)&c->ws_rstart, (R + 1) * sizeof(uint32_t));
-    // one entry per (sub-bin, region of its bin): kNFill x (R / 128) = R x kFinePerBin
-    if (e == hipSuccess && !c->ws_order) e = hipMalloc((void**)&c->ws_order, 3 * kNFill * sizeof(uint32_t));
-    if (e == hipSuccess && !c->ws_segend) e = hipMalloc((void**)&c->ws_segend, R * kFinePerBin * sizeof(uint32_t));
-    if (e == hipSuccess && !c->ws_tot) e = hipMalloc((void**)&c->ws_tot, (R + 1) * sizeof(uint32_t));
+    hipError_t e = hipSuccess;
+    const WsBufs bufs = ws_bufs(ws, max_reads, R);
+    for (const WsBuf& b : bufs.b)
+        if (e == hipSuccess && b.bytes && !*b.slot) e = hipMalloc(b.slot, b.bytes);
     if (e != hipSuccess) {
         ss_counter_release(c);
         ss_check(e, "ss_counter_reserve hipMalloc");
         return SS_ENOMEM;
     }
-    c->ws_reads = max_reads;
+    ws.reads = max_reads;
     return SS_OK;
 }
 
-uint64_t ss_counter_reserved(const ss_counter* c) { return c ? c->ws_reads : 0; }
+uint64_t ss_counter_reserved(const ss_counter* c) { return c ? c->ws.reads : 0; }
 
 int ss_counter_release(ss_counter* c) {
     if (!c) return ss_fail(SS_EARG, "null counter");
-    if (c->ws_keys) (void)hipFree(c->ws_keys);
-    if (c->ws_akey) (void)hipFree(c->ws_akey);
-    if (c->ws_aidx) (void)hipFree(c->ws_aidx);
-    if (c->ws_acnt) (void)hipFree(c->ws_acnt);
-    if (c->ws_areg) (void)hipFree(c->ws_areg);
-    if (c->ws_bidx) (void)hipFree(c->ws_bidx);
-    if (c->ws_bcnt) (void)hipFree(c->ws_bcnt);
-    if (c->ws_spill) (void)hipFree(c->ws_spill);
-    if (c->ws_words) (void)hipFree(c->ws_words);
-    c->ws_words = nullptr;
-    c->ws_words_cap = 0;
-    c->ws_keys = nullptr;
-    c->ws_akey = nullptr;
-    c->ws_aidx = nullptr;
-    c->ws_acnt = nullptr;
-    c->ws_areg = nullptr;
-    c->ws_bidx = nullptr;
-    c->ws_bcnt = nullptr;
-    c->ws_spill = nullptr;
-    c->ws_reads = 0;
-    c->ws_slab = 0;
-    c->ws_brecs = 0;
+    ws_free(ws_bufs(c->ws, 0, 0), 0, kWsBatch);
+    c->ws.words_cap = 0;
+    c->ws.reads = 0;
+    c->ws.slab = 0;
+    c->ws.brecs = 0;
     return SS_OK;
 }
 
-// words_in: pre-packed multi-word rows (ss_counter_insert_words; d_ascii / L / stride / d_first_bad
-// unused), else ASCII reads of length L
-static int insert_impl(ss_counter* c, const uint8_t* d_ascii, uint64_t n, uint32_t L, uint64_t stride,
-                       uint64_t base_index, uint64_t* d_first_bad, void* stream, const uint64_t* words_in,
-                       const uint64_t* keys_in = nullptr) {
-    hipStream_t s = (hipStream_t)stream;
-    int rc = SS_OK;
-    if (keys_in) {     // precomputed single-word keys: always partitioned
-        if (c->W != 1) return ss_fail(SS_EARG, "precomputed keys need a single-word handle");
-        if (n == 0) return SS_OK;
-        if (n > c->ws_reads && (rc = ss_counter_reserve(c, n)) != SS_OK) return rc;
+// Optimistic route: encode + coarse scatter in one pass (sub-bins reserved by atomics, no histogram
+// of the batch first), fine pass by sub-bin, aggregate per region, then whatever spilled.
+static int insert_optimistic(ss_counter* c, const InsertSrc& src, uint64_t n, uint64_t base_index,
+                             const InsertPlan& plan, hipStream_t s) {
+    const bool ascii = src.kind == InsertSrc::Kind::Ascii;
+    unsigned long long* first_bad = ascii ? (unsigned long long*)src.ascii.first_bad : nullptr;   // (keys: none)
+    // a pending reset: the aggregate writes whole slices (fresh) instead of a memset before it
+    const bool fresh = c->reset_pending;
+    c->reset_pending = false;
+    int rc = ss_check(lds_opt_in(), "hipFuncSetAttribute (dynamic LDS)");
+    if (rc) return rc;
+    const Tbl t = tbl_of(c);
+    PartWs w = part_ws(c);
+    uint32_t* fill = c->ws.kept.fill;
+    uint32_t* order = c->ws.kept.order;
+    const uint64_t cap1 = c->ws.cap1;
+    w.slab = plan.slab;
+    w.spill_ctr = fill + fill_at(kSpillCtr);
+    hipEvent_t tev[ss_counter::kPassEvents] = {};
+    for (uint32_t p = 0; p < ss_counter::kPassEvents; ++p) tev[p] = timer_event(c, p);
+    auto mark = [&](uint32_t p) {
+        if (tev[p]) (void)hipEventRecord(tev[p], s);
+    };
+    mark(0);
+    PrepWords pw{};   // first_bad reset with the sub-bin counters, in one dispatch
+    pw.p[0] = first_bad;
+    pw.v[0] = ~0ull;
+    pw.zero = fill;
+    pw.nzero = kFillWords;
+    rc = ss_check(launch_prep(pw, s), "first_bad / fill reset");
+    if (rc) return rc;
+    const dim3 grid(pf_resident_grid()), block(kPfT);
+    switch (plan.coarse) {
+    case Coarse::Keys:
+        hipLaunchKernelGGL((k_pf_coarse<kPfT, kPfRPL, true, false>), grid, block, 0, s, t, w, (const uint4*)src.keys,
+                           (uint64_t)0, n, 0u, cap1, fill, (unsigned long long*)nullptr);
+        break;
+    case Coarse::G16:     // 32-nt rows: coalesced lane-pair loads
+        hipLaunchKernelGGL((k_pf_coarse<kPfT, kPfRPL, false, true>), grid, block, 0, s, t, w,
+                           (const uint4*)src.ascii.rows, src.ascii.stride / 16, n, 2u, cap1, fill, first_bad);
+        break;
+    case Coarse::Plain:
+        hipLaunchKernelGGL((k_pf_coarse<kPfT, kPfRPL, false, false>), grid, block, 0, s, t, w,
+                           (const uint4*)src.ascii.rows, src.ascii.stride / 16, n, src.ascii.L / 16, cap1, fill,
+                           first_bad);
+        break;
     }
-    const uint32_t rb = c->log2cap - c->slice_log;
-    // the optimistic coarse partition below (the C5 path) resets first_bad with its sub-bin counters
-    const bool opt = !words_in && n > 0 && n <= c->ws_reads && rb > kCoarseBits && rb - kCoarseBits <= 8 &&
-                     (keys_in || (d_ascii && (L == 16 || L == 32) && stride % 16 == 0 && (((uintptr_t)d_ascii) & 15) == 0));
-    if (keys_in) {
-        // nothing to encode, no first_bad
-    } else if (!words_in) {
-        if (!d_first_bad) return ss_fail(SS_EARG, "d_first_bad is required");
-        if (stride < L) return ss_fail(SS_EARG, "stride < L");
-        if ((rc = fix_length(c, L))) return rc;
-        if (!opt) rc = ss_check(set_u64(d_first_bad, true, s), "reset first_bad");
-        if (rc || n == 0) return rc;
-        if (!d_ascii) return ss_fail(SS_EARG, "null buffer");
-    } else if (n == 0) {
-        return SS_OK;
+    const unsigned fine_blocks = kCB * kFinePerBin;
+    if (!w.slab) {   // counted cursors: region histogram per sub-bin, then the scans
+        hipLaunchKernelGGL((k_pf_count<512>), dim3(fine_blocks), dim3(512), 0, s, t, w, cap1, (const uint32_t*)fill);
+        const unsigned rg = (w.R + 255) / 256;
+        hipLaunchKernelGGL(k_pf_tot, dim3(rg), dim3(256), 0, s, w);
+        hipLaunchKernelGGL(k_pc_scan, dim3(1), dim3(1024), 0, s, w, w.R, w.rstart, (const uint32_t*)nullptr);
+        hipLaunchKernelGGL(k_pf_offsets, dim3(rg), dim3(256), 0, s, w);
+    }
+    w.seg_end = c->ws.kept.segend;
+    w.slabs = w.slab ? order + kNFill : nullptr;
+    mark(1);
+    hipLaunchKernelGGL(k_pf_order, dim3(1), dim3(512), 0, s, (const uint32_t*)fill, cap1, order,
+                       1u << (w.rbits - kCoarseBits), w.slab ? order + kNFill : nullptr);
+    mark(2);
+    hipLaunchKernelGGL((k_pf_scatter<kFsT, kFsTile>), dim3(fine_blocks), dim3(kFsT), 0, s, t, w, cap1,
+                       (const uint32_t*)fill, (const uint32_t*)order);
+    mark(3);
+    w.bkey = w.keys;
+    w.brec = (const Rec12*)w.keys;
+    hipLaunchKernelGGL((k_pc_aggregate_slice<kAggSliceT, true>), dim3(w.R), dim3(kAggSliceT),
+                       ((size_t)1 << c->slice_log) * 16, s, t, w, base_index, fresh);
+    mark(4);
+    // records that found their sub-bin full (none unless many distinct keys pile into a bin)
+    hipLaunchKernelGGL(k_spill_insert, dim3(1024), dim3(256), 0, s, t, w, (const uint32_t*)fill, base_index);
+    mark(5);
+    if (c->tev) {
+        c->thead = (c->thead + 1) % ss_counter::kTimerRing;
+        ++c->tpend;
+    }
+    c->occ_src = 1;   // the aggregate recorded the region occupancy
+    return ss_check(hipGetLastError(), "optimistic partitioned insert");
+}
+
+// Exact routes: keys and a per-block histogram of the whole batch, exact scatter offsets from its
+// scans, one scatter by region (<= 128 regions) or a coarse and a fine one, aggregate per region.
+// Single-word keys (Route::Exact) and multi-word keys (Route::ExactMulti: fingerprints of packed rows)
+// differ in the first and the last kernel and in how a pending reset is met.
+static int insert_exact(ss_counter* c, const InsertSrc& src, uint64_t n, uint64_t base_index, const InsertPlan& plan,
+                        hipStream_t s) {
+    const bool multi = plan.route == Route::ExactMulti;
+    const bool ascii = src.kind == InsertSrc::Kind::Ascii;
+    int rc = SS_OK;
+    const uint64_t* mw = nullptr;   // multi-word: the packed rows the passes read
+    bool fresh = false;
+    if (multi) {
+        // always partitioned: grow the workspace to this batch if needed
+        if (n > c->ws.reads && (rc = ss_counter_reserve(c, n)) != SS_OK) return rc;
+        if (ascii) {   // pack the reads into the word workspace first
+            const uint64_t need = c->ws.reads * c->W;
+            if (c->ws.words_cap < need) {
+                if (c->ws.batch.words) (void)hipFree(c->ws.batch.words);
+                c->ws.batch.words = nullptr;
+                c->ws.words_cap = 0;
+                if (hipMalloc((void**)&c->ws.batch.words, need * sizeof(uint64_t)) != hipSuccess) {
+                    ss_check(hipGetLastError(), "counter word workspace hipMalloc");
+                    return ss_fail(SS_ENOMEM, "counter word workspace: out of device memory");
+                }
+                c->ws.words_cap = need;
+            }
+            rc = ss_encode_fixed_impl(src.ascii.rows, n, src.ascii.L, src.ascii.stride, c->ws.batch.words, c->W,
+                                      src.ascii.first_bad, nullptr, nullptr, s);
+            if (rc) return rc;
+            mw = c->ws.batch.words;
+        } else {
+            mw = src.words;
+        }
+        if ((rc = flush_reset(c, s)) != SS_OK) return rc;   // k_mw_aggregate merges into the slots as they are
+    } else {
+        // keys of any length / layout k_pc_keys does not read: into the key workspace first
+        if (!plan.hist_keys && ascii)
+            rc = ss_encode_fixed_impl(src.ascii.rows, n, src.ascii.L, src.ascii.stride, c->ws.batch.keys, 1,
+                                      src.ascii.first_bad, nullptr, nullptr, s);
+        else if (!plan.hist_keys)
+            rc = ss_check(hipMemcpyAsync(c->ws.batch.keys, src.keys, n * 8, hipMemcpyDeviceToDevice, s),
+                          "counter key copy");
+        if (rc) return rc;
+        // a pending reset: the aggregate writes whole slices (fresh) instead of a memset before it
+        fresh = c->reset_pending;
+        c->reset_pending = false;
+    }
+    if ((rc = ss_check(lds_opt_in(), "hipFuncSetAttribute (dynamic LDS)"))) return rc;
+    const Tbl t = tbl_of(c);
+    PartWs w = part_ws(c);
+    const uint32_t bins1 = plan.two_pass ? kCB : w.R;
+    if (multi)
+        hipLaunchKernelGGL(kMwFp[mw_variant(t.W, mw)], dim3(kPartBlocks), dim3(kHistT), hist_lds_bytes(bins1, kHistT), s,
+                           t, w, bins1, mw, n);
+    else if (plan.hist_keys)
+        hipLaunchKernelGGL((k_pc_keys<kKeysT, kKeysU>), dim3(kPartBlocks), dim3(kKeysT), hist_lds_bytes(bins1, kKeysT),
+                           s, t, w, bins1, (const uint4*)src.ascii.rows, src.ascii.stride / 16, n, src.ascii.L / 16,
+                           (unsigned long long*)src.ascii.first_bad);
+    else
+        hipLaunchKernelGGL((k_pc_hist<kHistT>), dim3(kPartBlocks), dim3(kHistT), hist_lds_bytes(bins1, kHistT), s, t, w,
+                           bins1, n);
+    if (plan.two_pass) {
+        launch_scan(w, bins1, w.tot + 0, s);   // coarse starts are not needed later; tot is reused as scratch
+        hipLaunchKernelGGL((k_pc_scatter_lds<true, false>), dim3(kPartBlocks), dim3(512), 0, s, t, w, bins1,
+                           (const uint64_t*)w.keys, (const uint32_t*)nullptr, w.akey, w.aidx, n);
+        hipLaunchKernelGGL((k_pc_count<kCountT>), dim3(kPartBlocks), dim3(kCountT), 0, s, t, w, (const uint64_t*)w.akey,
+                           n);
+        launch_scan(w, w.R, w.rstart, s);
+        hipLaunchKernelGGL((k_pc_scatter_lds<false, true>), dim3(kPartBlocks), dim3(512), 0, s, t, w, w.R,
+                           (const uint64_t*)w.akey, (const uint32_t*)w.aidx, w.keys, w.bidx, n);
+        w.bkey = w.keys;
+    } else {
+        launch_scan(w, w.R, w.rstart, s);   // <= 128 regions: one pass, bins = regions (bin_of<true> == region)
+        hipLaunchKernelGGL((k_pc_scatter_lds<true, false>), dim3(kPartBlocks), dim3(512), 0, s, t, w, w.R,
+                           (const uint64_t*)w.keys, (const uint32_t*)nullptr, w.akey, w.bidx, n);
+        w.bkey = w.akey;
+    }
+    if (multi) {
+        const uint32_t S = 1u << c->slice_log;
+        hipLaunchKernelGGL(kMwAgg[mw_variant(t.W, mw)], dim3(w.R), dim3(kMwT), (size_t)2 * S * 16 + (size_t)S * 8, s, t, w,
+                           mw, base_index);
+    } else {
+        hipLaunchKernelGGL((k_pc_aggregate_slice<kAggSliceT, false>), dim3(w.R), dim3(kAggSliceT),
+                           ((size_t)1 << c->slice_log) * 16, s, t, w, base_index, fresh);
+        c->occ_src = 1;   // the single-word aggregate recorded the region occupancy
+    }
+    return ss_check(hipGetLastError(), "partitioned insert");
+}
+
+// Direct routes: no workspace that holds the batch; every read probes the table in HBM itself.
+static int insert_direct(ss_counter* c, const InsertSrc& src, uint64_t n, uint64_t base_index, const InsertPlan& plan,
+                         hipStream_t s) {
+    const InsertSrc::AsciiRows& a = src.ascii;
+    const int rc = flush_reset(c, s);
+    if (rc) return rc;
+    const Tbl t = tbl_of(c);
+    if (plan.route == Route::DirectG16) {
+        constexpr int U = 4;
+        const unsigned grid = grid_for(2 * n, (uint64_t)U * kThreads, 0);
+        hipLaunchKernelGGL((k_count_g16<U>), dim3(grid), dim3(kThreads), 0, s, t, (const uint4*)a.rows, a.stride / 16, n,
+                           a.L / 16, base_index, (unsigned long long*)a.first_bad);
+        return ss_check(hipGetLastError(), "k_count_g16");
+    }
+    const unsigned grid = grid_for(n, kThreads, 256 * 16);
+    hipLaunchKernelGGL(k_count_gen, dim3(grid), dim3(kThreads), 0, s, t, a.rows, a.stride, n, a.L, base_index,
+                       (unsigned long long*)a.first_bad);
+    return ss_check(hipGetLastError(), "k_count_gen");
+}
+
+static int insert_impl(ss_counter* c, const InsertSrc& src, uint64_t n, uint64_t base_index, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    const bool ascii = src.kind == InsertSrc::Kind::Ascii, keys = src.kind == InsertSrc::Kind::Keys;
+    int rc = SS_OK;
+    if (keys && c->W != 1) return ss_fail(SS_EARG, "precomputed keys need a single-word handle");
+    if (ascii) {
+        if (!src.ascii.first_bad) return ss_fail(SS_EARG, "d_first_bad is required");
+        if (src.ascii.stride < src.ascii.L) return ss_fail(SS_EARG, "stride < L");
+        if ((rc = fix_length(c, src.ascii.L))) return rc;
+    }
+    if (n == 0)   // an empty batch only resets first_bad
+        return ascii ? ss_check(set_u64(src.ascii.first_bad, true, s), "reset first_bad") : SS_OK;
+    // precomputed keys are always partitioned: grow the workspace to this batch if needed
+    if (keys && n > c->ws.reads && (rc = ss_counter_reserve(c, n)) != SS_OK) return rc;
+    const InsertPlan plan = plan_insert(c, src, n);
+    if (ascii) {
+        // first_bad: the optimistic route's k_prep resets it with the sub-bin counters; for every
+        // other route a stream write does, ahead of the checks below (an insert they refuse has reset it)
+        if (plan.route != Route::Optimistic) rc = ss_check(set_u64(src.ascii.first_bad, true, s), "reset first_bad");
+        if (rc) return rc;
+        if (!src.ascii.rows) return ss_fail(SS_EARG, "null buffer");
     }
     if (base_index > kMaxIndex || n - 1 > kMaxIndex - base_index)
         return ss_fail(SS_EARG, "global read indices of a counter handle must stay below 2^32 - 1");
@@ -3567,225 +3924,27 @@ static int insert_impl(ss_counter* c, const uint8_t* d_ascii, uint64_t n, uint32
     // ss_counter_spill_counts, and its class kernels read the slot counts directly)
     if (c->L != kWordKeys && c->since + n > c->spill_at && (rc = spill_wide(c, s))) return rc;
     c->since += n;
-    c->occ_src = 0;   // set again below by the paths whose aggregate records the region occupancy
-    Tbl t = tbl_of(c);
-    const bool multi = c->W > 1;
-    const bool fast = !words_in && !keys_in && (L == 16 || L == 32) && stride % 16 == 0 && (((uintptr_t)d_ascii) & 15) == 0;
-    const uint64_t* mw = words_in;          // the multi-word rows the partition passes read
-    if (multi) {
-        // multi-word keys: always partitioned; grow the workspace to this batch if needed
-        if (n > c->ws_reads && (rc = ss_counter_reserve(c, n)) != SS_OK) return rc;
+    c->occ_src = 0;   // stale, unless the route's aggregate records the region occupancy
+    c->last_route = route_code(plan);
+    switch (plan.route) {
+    case Route::Optimistic: return insert_optimistic(c, src, n, base_index, plan, s);
+    case Route::Exact:
+    case Route::ExactMulti: return insert_exact(c, src, n, base_index, plan, s);
+    case Route::DirectG16:
+    case Route::DirectGeneric: return insert_direct(c, src, n, base_index, plan, s);
     }
-    if (multi && !words_in) {
-        const uint64_t need = c->ws_reads * c->W;
-        if (c->ws_words_cap < need) {
-            if (c->ws_words) (void)hipFree(c->ws_words);
-            c->ws_words = nullptr;
-            c->ws_words_cap = 0;
-            if (hipMalloc((void**)&c->ws_words, need * sizeof(uint64_t)) != hipSuccess) {
-                ss_check(hipGetLastError(), "counter word workspace hipMalloc");
-                return ss_fail(SS_ENOMEM, "counter word workspace: out of device memory");
-            }
-            c->ws_words_cap = need;
-        }
-        rc = ss_encode_fixed_impl(d_ascii, n, L, stride, c->ws_words, c->W, d_first_bad, nullptr, nullptr, stream);
-        if (rc) return rc;
-        mw = c->ws_words;
-    }
-    // single-word keys of any other length / layout: pack into the key workspace first, then the
-    // same partitioned passes (k_pc_hist replaces the fused encode of k_pc_keys)
-    const bool packed_keys = !multi && !fast && n <= c->ws_reads;
-    if (packed_keys && keys_in && !opt) {
-        rc = ss_check(hipMemcpyAsync(c->ws_keys, keys_in, n * 8, hipMemcpyDeviceToDevice, s), "counter key copy");
-        if (rc) return rc;
-    } else if (packed_keys && !keys_in) {
-        rc = ss_encode_fixed_impl(d_ascii, n, L, stride, c->ws_keys, 1, d_first_bad, nullptr, nullptr, stream);
-        if (rc) return rc;
-    }
-    const bool part = multi || packed_keys || (fast && n <= c->ws_reads);
-    // a pending reset: the single-word aggregate writes whole slices (fresh); other paths memset first
-    bool fresh = false;
-    if (part && !multi) {
-        fresh = c->reset_pending;
-        c->reset_pending = false;
-    } else if ((rc = flush_reset(c, s)) != SS_OK) {
-        return rc;
-    }
-    if (part) {
-        PartWs w;
-        w.keys = c->ws_keys;
-        w.akey = c->ws_akey;
-        w.aidx = c->ws_aidx;
-        w.acnt = c->ws_acnt;
-        w.areg = c->ws_areg;
-        w.bidx = c->ws_bidx;
-        w.bcnt = c->ws_bcnt;
-        w.spill = c->ws_spill;
-        w.spill_cap = c->ws_reads;
-        w.seg_end = nullptr;
-        w.hist = c->ws_hist;
-        w.rstart = c->ws_rstart;
-        w.tot = c->ws_tot;
-        w.bkey = nullptr;
-        w.brec = nullptr;
-        w.slab = 0;
-        w.slabs = nullptr;
-        w.spill_ctr = nullptr;
-        w.R = (uint32_t)(c->cap >> c->slice_log);
-        w.rbits = c->log2cap - c->slice_log;
-        const uint32_t S = 1u << c->slice_log;
-        const size_t mw_lds = (size_t)2 * S * 16 + (size_t)S * 8;
-        const bool two_pass = w.rbits > kCoarseBits;             // > 64 regions: coarse pass first
-        const uint32_t bins1 = two_pass ? (1u << kCoarseBits) : w.R;
-        constexpr int T1 = 512, U1 = 2, TS = 512, TF = 512;
-        // dynamic LDS above the 64 KB default: opt in once per kernel (host-side attribute; a
-        // function-local static is initialised once even with engines on several threads)
-        static const hipError_t attrs = [] {
-            const int agg_max = (int)(2 * (1u << kMwSliceLog) * 16 + (1u << kMwSliceLog) * 8 + 8);
-            hipError_t ea = hipFuncSetAttribute((const void*)k_pc_keys<T1, U1>,
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, kMaxRegions * 4);
-            if (ea == hipSuccess)
-                ea = hipFuncSetAttribute((const void*)k_pc_hist<TF>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                         kMaxRegions * 4);
-            for (int f = 0; f < kMwAggFns && ea == hipSuccess; ++f)
-                ea = hipFuncSetAttribute((const void*)kMwFp[f], hipFuncAttributeMaxDynamicSharedMemorySize,
-                                         kMaxRegions * 4);
-            for (int f = 0; f < kMwAggFns && ea == hipSuccess; ++f)
-                ea = hipFuncSetAttribute((const void*)kMwAgg[f], hipFuncAttributeMaxDynamicSharedMemorySize, agg_max);
-
-            return ea;
-        }();
-        if (attrs != hipSuccess) return ss_check(attrs, "hipFuncSetAttribute (dynamic LDS)");
-        auto scan = [&](uint32_t bins, uint32_t* start) {
-            hipLaunchKernelGGL(k_pc_tot, dim3(bins), dim3(256), 0, s, w, bins);
-            hipLaunchKernelGGL(k_pc_scan, dim3(1), dim3(1024), 0, s, w, bins, start);
-            hipLaunchKernelGGL(k_pc_offsets, dim3(bins), dim3(1024), 0, s, w, bins, (const uint32_t*)start);
-        };
-        if (!multi && (!packed_keys || (keys_in && opt)) && two_pass && w.rbits - kCoarseBits <= 8) {
-            // optimistic coarse partition: encode + coarse scatter in one pass, fine pass by bin
-            const uint64_t cap1 = c->ws_cap1;
-            w.slab = (uint32_t)c->ws_slab;
-            w.spill_ctr = c->ws_fill + fill_at(kSpillCtr);
-            hipEvent_t tev[ss_counter::kPassEvents] = {};
-            for (uint32_t p = 0; p < ss_counter::kPassEvents; ++p) tev[p] = timer_event(c, p);
-            auto mark = [&](uint32_t p) {
-                if (tev[p]) (void)hipEventRecord(tev[p], s);
-            };
-            mark(0);
-            PrepWords pw{};
-            pw.p[0] = (unsigned long long*)d_first_bad;
-            pw.v[0] = ~0ull;
-            pw.zero = c->ws_fill;
-            pw.nzero = kFillWords;
-            rc = ss_check(launch_prep(pw, s), "first_bad / fill reset");
-            if (rc) return rc;
-            // grid-stride over tiles: exactly the resident blocks (no second, partial round)
-            static const int pf_grid = [] {
-                int dev = 0, cus = 0, per = 0;
-                (void)hipGetDevice(&dev);
-                (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-                (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, (const void*)k_pf_coarse<kPfT, kPfRPL, false, true>, kPfT, 0);
-                return (cus > 0 && per > 0) ? cus * per : (int)kPartBlocks;
-            }();
-            if (keys_in)
-                hipLaunchKernelGGL((k_pf_coarse<kPfT, kPfRPL, true, false>), dim3(pf_grid), dim3(kPfT), 0, s, t, w,
-                                   (const uint4*)keys_in, (uint64_t)0, n, 0u, cap1, c->ws_fill,
-                                   (unsigned long long*)nullptr);
-            else if (L == 32)     // 32-nt rows: coalesced lane-pair loads (G16)
-                hipLaunchKernelGGL((k_pf_coarse<kPfT, kPfRPL, false, true>), dim3(pf_grid), dim3(kPfT), 0, s, t, w,
-                                   (const uint4*)d_ascii, stride / 16, n, 2u, cap1, c->ws_fill,
-                                   (unsigned long long*)d_first_bad);
-            else
-                hipLaunchKernelGGL((k_pf_coarse<kPfT, kPfRPL, false, false>), dim3(pf_grid), dim3(kPfT), 0, s, t, w,
-                                   (const uint4*)d_ascii, stride / 16, n, L / 16, cap1, c->ws_fill,
-                                   (unsigned long long*)d_first_bad);
-            const unsigned fine_blocks = kCB * kFinePerBin;
-            if (!w.slab) {   // counted cursors: region histogram per sub-bin, then the scans
-                hipLaunchKernelGGL((k_pf_count<512>), dim3(fine_blocks), dim3(512), 0, s, t, w, cap1,
-                                   (const uint32_t*)c->ws_fill);
-                const unsigned rg = (w.R + 255) / 256;
-                hipLaunchKernelGGL(k_pf_tot, dim3(rg), dim3(256), 0, s, w);
-                hipLaunchKernelGGL(k_pc_scan, dim3(1), dim3(1024), 0, s, w, w.R, w.rstart, (const uint32_t*)nullptr);
-                hipLaunchKernelGGL(k_pf_offsets, dim3(rg), dim3(256), 0, s, w);
-            }
-            w.seg_end = c->ws_segend;
-            w.slabs = w.slab ? c->ws_order + kNFill : nullptr;
-            mark(1);
-            hipLaunchKernelGGL(k_pf_order, dim3(1), dim3(512), 0, s, (const uint32_t*)c->ws_fill, cap1, c->ws_order,
-                               1u << (w.rbits - kCoarseBits), w.slab ? c->ws_order + kNFill : nullptr);
-            mark(2);
-            hipLaunchKernelGGL((k_pf_scatter<kFsT, kFsTile>), dim3(fine_blocks), dim3(kFsT), 0, s, t, w, cap1,
-                               (const uint32_t*)c->ws_fill, (const uint32_t*)c->ws_order);
-            mark(3);
-            w.bkey = w.keys;
-            w.brec = (const Rec12*)w.keys;
-            hipLaunchKernelGGL((k_pc_aggregate_slice<kAggSliceT, true>), dim3(w.R), dim3(kAggSliceT),
-                               ((size_t)1 << c->slice_log) * 16, s, t, w, base_index, fresh);
-            mark(4);
-            // records that found their sub-bin full (none unless many distinct keys pile into a bin)
-            hipLaunchKernelGGL(k_spill_insert, dim3(1024), dim3(256), 0, s, t, w, (const uint32_t*)c->ws_fill,
-                               base_index);
-            mark(5);
-            if (c->tev) {
-                c->thead = (c->thead + 1) % ss_counter::kTimerRing;
-                ++c->tpend;
-            }
-            c->occ_src = 1;
-            return ss_check(hipGetLastError(), "optimistic partitioned insert");
-        }
-        if (multi) {
-            const size_t fp_lds = (bins1 * (TF / 64) <= kMaxRegions ? bins1 * (TF / 64) : bins1) * 4;
-            static_assert(TF == kMwFpT, "k_mw_fp instances");
-            hipLaunchKernelGGL(kMwFp[mw_variant(t.W, mw)], dim3(kPartBlocks), dim3(TF), fp_lds, s, t, w, bins1, mw, n);
-        } else if (packed_keys) {
-            const size_t h_lds = (bins1 * (TF / 64) <= kMaxRegions ? bins1 * (TF / 64) : bins1) * 4;
-            hipLaunchKernelGGL((k_pc_hist<TF>), dim3(kPartBlocks), dim3(TF), h_lds, s, t, w, bins1, n);
-        } else {
-            const size_t keys_lds = (bins1 * (T1 / 64) <= kMaxRegions ? bins1 * (T1 / 64) : bins1) * 4;
-            hipLaunchKernelGGL((k_pc_keys<T1, U1>), dim3(kPartBlocks), dim3(T1), keys_lds, s, t, w, bins1,
-                               (const uint4*)d_ascii, stride / 16, n, L / 16, (unsigned long long*)d_first_bad);
-        }
-        if (two_pass) {
-            scan(bins1, w.tot + 0);   // coarse starts are not needed later; tot is reused as scratch
-            hipLaunchKernelGGL((k_pc_scatter_lds<true, false>), dim3(kPartBlocks), dim3(512), 0, s, t, w, bins1,
-                               (const uint64_t*)w.keys, (const uint32_t*)nullptr, w.akey, w.aidx, n);
-            hipLaunchKernelGGL((k_pc_count<TS>), dim3(kPartBlocks), dim3(TS), 0, s, t, w, (const uint64_t*)w.akey, n);
-            scan(w.R, w.rstart);
-            hipLaunchKernelGGL((k_pc_scatter_lds<false, true>), dim3(kPartBlocks), dim3(512), 0, s, t, w, w.R,
-                               (const uint64_t*)w.akey, (const uint32_t*)w.aidx, w.keys, w.bidx, n);
-            w.bkey = w.keys;
-        } else {
-            scan(w.R, w.rstart);   // <= 64 regions: one pass, bins = regions (bin_of<true> == region)
-            hipLaunchKernelGGL((k_pc_scatter_lds<true, false>), dim3(kPartBlocks), dim3(512), 0, s, t, w, w.R,
-                               (const uint64_t*)w.keys, (const uint32_t*)nullptr, w.akey, w.bidx, n);
-            w.bkey = w.akey;
-        }
-        if (multi)
-            hipLaunchKernelGGL(kMwAgg[mw_variant(t.W, mw)], dim3(w.R), dim3(kMwT), mw_lds, s, t, w, mw, base_index);
-        else
-            hipLaunchKernelGGL((k_pc_aggregate_slice<kAggSliceT, false>), dim3(w.R), dim3(kAggSliceT),
-                               ((size_t)1 << c->slice_log) * 16, s, t, w, base_index, fresh);
-        if (!multi) c->occ_src = 1;
-        return ss_check(hipGetLastError(), "partitioned insert");
-    }
-    if (fast) {
-        constexpr int U = 4;
-        const unsigned grid = grid_for(2 * n, (uint64_t)U * kThreads, 0);
-        hipLaunchKernelGGL((k_count_g16<U>), dim3(grid), dim3(kThreads), 0, s, t, (const uint4*)d_ascii,
-                           stride / 16, n, L / 16, base_index, (unsigned long long*)d_first_bad);
-        return ss_check(hipGetLastError(), "k_count_g16");
-    }
-    const unsigned grid = grid_for(n, kThreads, 256 * 16);
-    hipLaunchKernelGGL(k_count_gen, dim3(grid), dim3(kThreads), 0, s, t, d_ascii, stride, n, L, base_index,
-                       (unsigned long long*)d_first_bad);
-    return ss_check(hipGetLastError(), "k_count_gen");
+    return ss_fail(SS_EARG, "insert route");
 }
+
+int ss_counter_last_route(const ss_counter* c) { return c ? c->last_route : -1; }
 
 int ss_counter_insert_fixed(ss_counter* c, const uint8_t* d_ascii, uint64_t n, uint32_t L,
                             uint64_t stride, uint64_t base_index, uint64_t* d_first_bad, void* stream) {
     if (!c) return ss_fail(SS_EARG, "null counter");
     if (c->L == kWordKeys) return ss_fail(SS_EARG, "the handle holds packed multi-word keys (ss_counter_insert_words)");
-    return insert_impl(c, d_ascii, n, L, stride, base_index, d_first_bad, stream, nullptr);
+    InsertSrc src{InsertSrc::Kind::Ascii, {}};
+    src.ascii = {d_ascii, L, stride, d_first_bad};
+    return insert_impl(c, src, n, base_index, stream);
 }
 
 int ss_counter_set_words(ss_counter* c, uint32_t W) {
@@ -3793,16 +3952,8 @@ int ss_counter_set_words(ss_counter* c, uint32_t W) {
     if (W < 2 || W > 64) return ss_fail(SS_EARG, "packed keys of 2..64 words");
     if (c->L == kWordKeys && c->W == W) return SS_OK;
     if (c->L != -1) return ss_fail(SS_EARG, "the handle already holds keys of another kind");
-    if (c->keywords_W != W) {
-        if (c->keywords) (void)hipFree(c->keywords);
-        c->keywords = nullptr;
-        c->keywords_W = 0;
-        if (hipMalloc((void**)&c->keywords, c->cap * W * sizeof(uint64_t)) != hipSuccess) {
-            ss_check(hipGetLastError(), "counter key words hipMalloc");
-            return ss_fail(SS_ENOMEM, "counter key words: out of device memory");
-        }
-        c->keywords_W = W;
-    }
+    const int rc = alloc_keywords(c, W);
+    if (rc) return rc;
     c->W = W;
     c->L = kWordKeys;
     return SS_OK;
@@ -3812,7 +3963,9 @@ int ss_counter_insert_words(ss_counter* c, const uint64_t* d_words, uint64_t n, 
     if (!c) return ss_fail(SS_EARG, "null counter");
     if (c->L != kWordKeys) return ss_fail(SS_EARG, "ss_counter_set_words first");
     if (n && !d_words) return ss_fail(SS_EARG, "null buffer");
-    return insert_impl(c, nullptr, n, 0, 0, base_index, nullptr, stream, d_words);
+    InsertSrc src{InsertSrc::Kind::Words, {}};
+    src.words = d_words;
+    return insert_impl(c, src, n, base_index, stream);
 }
 
 int ss_counter_insert_keys(ss_counter* c, const uint64_t* d_keys, uint64_t n, uint64_t base_index, void* stream) {
@@ -3822,7 +3975,9 @@ int ss_counter_insert_keys(ss_counter* c, const uint64_t* d_keys, uint64_t n, ui
         const int rc = fix_length(c, 32);
         if (rc) return rc;
     }
-    return insert_impl(c, nullptr, n, 0, 0, base_index, nullptr, stream, nullptr, d_keys);
+    InsertSrc src{InsertSrc::Kind::Keys, {}};
+    src.keys = d_keys;
+    return insert_impl(c, src, n, base_index, stream);
 }
 
 int ss_counter_merge(ss_counter* c, const uint64_t* d_keys, const uint32_t* d_lens,

@@ -56,6 +56,11 @@ extern "C" int ss_short_keys_impl(const uint8_t* d_buf, const uint64_t* d_offs, 
 // optimistic partitioned insert (12-B records, LDS aggregation) -- e.g. the class rows' fingerprints.
 extern "C" int ss_counter_insert_keys(ss_counter* c, const uint64_t* d_keys, uint64_t n, uint64_t base_index,
                                       void* stream);
+// The kernel chain the handle's last insert took (for tests that pin the dispatch), -1 before any:
+// bits 0-2 the route (0 optimistic, 1 exact, 2 exact multi-word, 3 direct g16, 4 direct generic),
+// 8 = two exact scatter passes, 16 = histogram by k_pc_keys (else k_pc_hist), bits 5-6 the
+// optimistic coarse kernel (0 plain, 1 G16, 2 keys), 128 = fine-scatter slabs (else counted cursors).
+extern "C" int ss_counter_last_route(const ss_counter* c);
 // One length class of the drop-in engine's chunk for ss_classes_verify_fold: its table (set_words(W1)),
 // its m packed rows of W1 words, and the table's first row index for them.
 struct ss_class_rows {

@@ -29,15 +29,15 @@ int main(int argc, char** argv) {
     CS(ss_counter_set_length(c, 32));
     Tbl t = tbl_of(c);
     PartWs w{};
-    w.akey = c->ws_akey;
-    w.acnt = c->ws_acnt;
-    w.areg = c->ws_areg;
-    w.spill = c->ws_spill;
-    w.spill_cap = c->ws_reads;
+    w.akey = c->ws.batch.akey;
+    w.acnt = c->ws.batch.acnt;
+    w.areg = c->ws.batch.areg;
+    w.spill = c->ws.batch.spill;
+    w.spill_cap = c->ws.reads;
     w.R = (uint32_t)(c->cap >> c->slice_log);
     w.rbits = c->log2cap - c->slice_log;
-    w.slab = (uint32_t)c->ws_slab;
-    w.spill_ctr = c->ws_fill + fill_at(kSpillCtr);
+    w.slab = (uint32_t)c->ws.slab;
+    w.spill_ctr = c->ws.kept.fill + fill_at(kSpillCtr);
     int dev = 0, cus = 0, per = 0;
     CK(hipGetDevice(&dev));
     CK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
@@ -48,11 +48,11 @@ int main(int argc, char** argv) {
     CK(hipEventCreate(&e1));
     std::vector<float> ts;
     for (int r = -3; r < reps; ++r) {
-        CK(hipMemsetAsync(c->ws_fill, 0, kFillWords * sizeof(uint32_t), 0));
+        CK(hipMemsetAsync(c->ws.kept.fill, 0, kFillWords * sizeof(uint32_t), 0));
         CK(hipMemsetAsync(fb, 0xFF, 8, 0));
         CK(hipEventRecord(e0, 0));
         hipLaunchKernelGGL((k_pf_coarse<kPfT, kPfRPL, false, true>), dim3(grid), dim3(kPfT), 0, 0, t, w,
-                           (const uint4*)ascii, (uint64_t)2, n, 2u, c->ws_cap1, c->ws_fill, (unsigned long long*)fb);
+                           (const uint4*)ascii, (uint64_t)2, n, 2u, c->ws.cap1, c->ws.kept.fill, (unsigned long long*)fb);
         CK(hipEventRecord(e1, 0));
         CK(hipEventSynchronize(e1));
         float ms = 0;

@@ -20,13 +20,13 @@
 namespace {
 PartWs ws_of(ss_counter* c) {
     PartWs w{};
-    w.keys = c->ws_keys; w.akey = c->ws_akey; w.aidx = c->ws_aidx; w.acnt = c->ws_acnt; w.areg = c->ws_areg;
-    w.bidx = c->ws_bidx; w.bcnt = c->ws_bcnt; w.spill = c->ws_spill; w.spill_cap = c->ws_reads;
-    w.hist = c->ws_hist; w.rstart = c->ws_rstart; w.tot = c->ws_tot;
+    w.keys = c->ws.batch.keys; w.akey = c->ws.batch.akey; w.aidx = c->ws.batch.aidx; w.acnt = c->ws.batch.acnt; w.areg = c->ws.batch.areg;
+    w.bidx = c->ws.batch.bidx; w.bcnt = c->ws.batch.bcnt; w.spill = c->ws.batch.spill; w.spill_cap = c->ws.reads;
+    w.hist = c->ws.kept.hist; w.rstart = c->ws.kept.rstart; w.tot = c->ws.kept.tot;
     w.R = (uint32_t)(c->cap >> c->slice_log); w.rbits = c->log2cap - c->slice_log;
-    w.slab = 1; w.spill_ctr = c->ws_fill + fill_at(kSpillCtr);
-    w.seg_end = c->ws_segend;
-    w.slabs = c->ws_order + kNFill;
+    w.slab = 1; w.spill_ctr = c->ws.kept.fill + fill_at(kSpillCtr);
+    w.seg_end = c->ws.kept.segend;
+    w.slabs = c->ws.kept.order + kNFill;
     return w;
 }
 
@@ -36,18 +36,18 @@ int g_mul = 1;
 void coarse(ss_counter* c, const uint8_t* ascii, uint64_t n, uint64_t* fb, hipStream_t s) {
     Tbl t = tbl_of(c);
     PartWs w = ws_of(c);
-    CK(hipMemsetAsync(c->ws_fill, 0, kFillWords * sizeof(uint32_t), s));
+    CK(hipMemsetAsync(c->ws.kept.fill, 0, kFillWords * sizeof(uint32_t), s));
     hipLaunchKernelGGL((k_pf_coarse<kPfT, kPfRPL, false, false>), dim3(g_grid * g_mul), dim3(kPfT), 0, s, t, w, (const uint4*)ascii,
-                       (uint64_t)2, n, 2u, c->ws_cap1, c->ws_fill, (unsigned long long*)fb);
+                       (uint64_t)2, n, 2u, c->ws.cap1, c->ws.kept.fill, (unsigned long long*)fb);
 }
 
 void fine(ss_counter* c, hipStream_t s) {
     Tbl t = tbl_of(c);
     PartWs w = ws_of(c);
-    hipLaunchKernelGGL(k_pf_order, dim3(1), dim3(512), 0, s, (const uint32_t*)c->ws_fill, c->ws_cap1, c->ws_order,
-                       1u << (w.rbits - kCoarseBits), c->ws_order + kNFill);
-    hipLaunchKernelGGL((k_pf_scatter<kFsT, kFsTile>), dim3(kNFill), dim3(kFsT), 0, s, t, w, c->ws_cap1,
-                       (const uint32_t*)c->ws_fill, (const uint32_t*)c->ws_order);
+    hipLaunchKernelGGL(k_pf_order, dim3(1), dim3(512), 0, s, (const uint32_t*)c->ws.kept.fill, c->ws.cap1, c->ws.kept.order,
+                       1u << (w.rbits - kCoarseBits), c->ws.kept.order + kNFill);
+    hipLaunchKernelGGL((k_pf_scatter<kFsT, kFsTile>), dim3(kNFill), dim3(kFsT), 0, s, t, w, c->ws.cap1,
+                       (const uint32_t*)c->ws.kept.fill, (const uint32_t*)c->ws.kept.order);
 }
 }  // namespace
 

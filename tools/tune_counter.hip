@@ -73,14 +73,14 @@ int main(int argc, char** argv) {
     CK(hipMemcpy(&hs, size, 8, hipMemcpyDeviceToHost));
     CK(hipMemcpy(&hfb, fb, 8, hipMemcpyDeviceToHost));
     uint32_t hspill = 0;
-    CK(hipMemcpy(&hspill, c->ws_fill + fill_at(kSpillCtr), 4, hipMemcpyDeviceToHost));
-    if (getenv("SS_DIAG") && c->ws_slab && hspill) {   // where do the spills come from
+    CK(hipMemcpy(&hspill, c->ws.kept.fill + fill_at(kSpillCtr), 4, hipMemcpyDeviceToHost));
+    if (getenv("SS_DIAG") && c->ws.slab && hspill) {   // where do the spills come from
         const uint32_t nb = (uint32_t)((c->cap >> c->slice_log) >> kCoarseBits);
         std::vector<uint32_t> sl(2 * kNFill), hist((size_t)kNFill * nb), se((size_t)kNFill * nb), fl(kFillWords);
-        CK(hipMemcpy(sl.data(), c->ws_order + kNFill, sl.size() * 4, hipMemcpyDeviceToHost));
-        CK(hipMemcpy(hist.data(), c->ws_hist, hist.size() * 4, hipMemcpyDeviceToHost));
-        CK(hipMemcpy(se.data(), c->ws_segend, se.size() * 4, hipMemcpyDeviceToHost));
-        CK(hipMemcpy(fl.data(), c->ws_fill, fl.size() * 4, hipMemcpyDeviceToHost));
+        CK(hipMemcpy(sl.data(), c->ws.kept.order + kNFill, sl.size() * 4, hipMemcpyDeviceToHost));
+        CK(hipMemcpy(hist.data(), c->ws.kept.hist, hist.size() * 4, hipMemcpyDeviceToHost));
+        CK(hipMemcpy(se.data(), c->ws.kept.segend, se.size() * 4, hipMemcpyDeviceToHost));
+        CK(hipMemcpy(fl.data(), c->ws.kept.fill, fl.size() * 4, hipMemcpyDeviceToHost));
         uint64_t full = 0, fullfb = 0;
         for (uint32_t f = 0; f < kNFill; ++f) {
             uint32_t nf = 0;
@@ -89,8 +89,8 @@ int main(int argc, char** argv) {
             fullfb += nf > 0;
             if (nf && fullfb <= 6) printf("  fb %u fill %u slab %u full regions %u\n", f, fl[fill_at(f)], sl[kNFill + f], nf);
         }
-        std::vector<uint4> sp(std::min<uint64_t>(hspill, c->ws_reads));
-        CK(hipMemcpy(sp.data(), c->ws_spill, sp.size() * 16, hipMemcpyDeviceToHost));
+        std::vector<uint4> sp(std::min<uint64_t>(hspill, c->ws.reads));
+        CK(hipMemcpy(sp.data(), c->ws.batch.spill, sp.size() * 16, hipMemcpyDeviceToHost));
         std::unordered_map<uint64_t, uint64_t> kc;
         uint64_t weighted = 0;
         for (auto& r : sp) { kc[((uint64_t)r.y << 32) | r.x] += 1; weighted += r.z > 1; }
