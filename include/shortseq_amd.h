@@ -133,6 +133,10 @@ int ss_encode_hamming_ref(const uint8_t* d_ascii, uint64_t n, uint32_t L, uint64
  * fixed: one (start, len) for the batch, start + len <= L.
  * var:   per-read d_starts / d_lens; with d_read_lens (nullable) they are clamped to the read
  *        (start' = min(start, L_r), len' = min(len, L_r - start')), as Python slice bounds are.
+ *        Without d_read_lens they are any u32: a start at or past 32*wpr gives a zero row, and a len
+ *        past the row's wpr words ends there (whatever those words hold past the read is copied).
+ *        out_wpr may be smaller than ceil(len/32): the row then holds the first 32*out_wpr nts of
+ *        the slice.
  * ---------------------------------------------------------------------------------------------- */
 int ss_slice_fixed(const uint64_t* d_words, uint64_t n, uint32_t L, uint32_t wpr, uint32_t start, uint32_t len,
                    uint64_t* d_out, uint32_t out_wpr, void* stream);

@@ -1123,14 +1123,17 @@ __global__ __launch_bounds__(kThreads) void k_slice(const uint64_t* __restrict__
             st = min(st, L);
             ln = min(ln, L - st);
         }
-        const uint32_t bits = 2u * ln;
+        // st / ln are any u32 (a caller's int32 arithmetic gone negative), so neither is doubled
+        // whole: 2 * 2^31 would wrap to "from nt 0" / "0 nts".  Word and bit offset come from st's
+        // two fields and the slice's end is tested in nts; a start past the row finds w >= wpr (a
+        // zero row), a len past it ends with the row's words.
         uint64_t v = 0;
-        if (64u * i < bits) {
-            const uint32_t bit = 2u * st + 64u * i, w = bit >> 6, o = bit & 63u;
+        if (32u * i < ln) {
+            const uint32_t w = (st >> 5) + i, o = 2u * (st & 31u);
             const uint64_t* s = src + r * wpr;
             v = (w < wpr ? s[w] : 0ull) >> o;
             if (o && w + 1 < wpr) v |= s[w + 1] << (64u - o);
-            const uint32_t rem = bits - 64u * i;
+            const uint32_t rem = 2u * min(ln - 32u * i, 32u);      // bits of the slice in this word
             if (rem < 64u) v &= (1ull << rem) - 1ull;
         }
         out[r * out_wpr + i] = v;
