@@ -13,7 +13,8 @@
  *     Exceptions, each documented at its declaration: the counter and ingest handles (their own
  *     workspaces; the ingest calls are synchronous), and ss_hamming_all_pairs / _ex when they take
  *     the pigeonhole / bucketed form (a per-device scratch buffer cached across calls; AUTO reads its
- *     candidate totals back with one stream sync).  SS_ALLPAIRS_TILES keeps the plain contract.
+ *     candidate totals back with one stream sync), and ss_cluster_pairs (one stream sync per round;
+ *     never capturable).  SS_ALLPAIRS_TILES keeps the plain contract.
  *   - Validation mirrors util.pxd:98-99 (bloom filter 0xFFFFFFFFFFEFFF75, util.pyx:75).  A kernel
  *     that meets an invalid byte writes the index of the FIRST invalid read (input order) into
  *     *d_first_bad (atomicMin; the entry point resets it to UINT64_MAX first).  The caller re-scans
@@ -183,6 +184,43 @@ int ss_hamming_all_pairs(const uint64_t* d_words, uint64_t n, uint32_t L, uint32
 int ss_hamming_all_pairs_ex(const uint64_t* d_words, uint64_t n, uint32_t L, uint32_t wpr, uint32_t max_dist,
                             uint32_t* d_counts, uint32_t* d_pairs, uint64_t max_pairs, uint64_t* d_npairs,
                             uint32_t method, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * UMI clustering over a pair list (the step after ss_hamming_all_pairs* in a UMI dedup; new in this ABI
+ * version, replaces no reference interface — the reference's shortseq/umi/ package is unfinished).
+ * n < 2^32 nodes (distinct UMIs), m undirected pairs (i, j) as two u32 each (any order, duplicates
+ * harmless; d_pairs 8-B aligned), optionally a count per node (u64, <= 2^62).  d_order = the nodes by
+ * count descending, ties by ascending index (a stable descending sort; NULL = identity; trusted to be
+ * a permutation); rank = its inverse.  Methods, named as in UMI-tools:
+ *   COMPONENTS  ("cluster"): a node's representative is the lowest-rank node of its connected component.
+ *   DIRECTIONAL: a pair gives the edge u -> v iff c[u] + 1 >= 2 c[v] (UMI-tools' c[u] >= 2 c[v] - 1;
+ *                both directions may hold); a node's representative is the lowest-rank node among
+ *                itself and its directed ancestors, which is the group UMI-tools' count-ordered BFS
+ *                with first-observation-wins puts it in.
+ * UMI-tools' `adjacency` method (a sequential greedy cover) is not provided.
+ * Outputs: d_rep[v] = v's representative; d_sizes / d_sums (nullable; d_sums needs d_counts): a
+ * cluster's size and u64 count sum at its representative's index, 0 elsewhere; *d_nclusters.
+ * ss_cluster_pairs allocates no device memory: the caller supplies d_ws (8-B aligned,
+ * ss_cluster_ws_bytes(n, m) bytes).  It is NOT capturable and not asynchronous: rounds (a pass over the
+ * pairs, a pass over the nodes) repeat until one lowers no label, and the host reads that flag once per
+ * round, synchronising with `stream` (through a 16-B pinned word per host thread, made at the thread's
+ * first call; SS_ENOMEM if that fails); on a capturing stream it returns SS_EARG.  *h_rounds (nullable)
+ * = rounds run, the last, idle one included (0 when m = 0).  The outputs are queued on `stream`.
+ * SS_EARG: n >= 2^32, a workspace too small, DIRECTIONAL or d_sums without d_counts (n > 0), an unknown
+ * method, or a pair naming a node >= n (never dereferenced: the pair is skipped, the call returns after
+ * its first round and the outputs are unspecified).
+ * ss_host_cluster_pairs: the same function in plain C++ on host arrays (union-find / a worklist), for
+ * small inputs and hosts without a GPU; the same SS_EARG cases, checked before anything is written.
+ * ---------------------------------------------------------------------------------------------- */
+#define SS_CLUSTER_COMPONENTS 0u
+#define SS_CLUSTER_DIRECTIONAL 1u
+uint64_t ss_cluster_ws_bytes(uint64_t n, uint64_t m);
+int ss_cluster_pairs(const uint32_t* d_pairs, uint64_t m, uint64_t n, const uint64_t* d_counts, const uint32_t* d_order,
+                     uint32_t method, void* d_ws, uint64_t ws_bytes, uint32_t* d_rep, uint32_t* d_sizes, uint64_t* d_sums,
+                     uint64_t* d_nclusters, uint32_t* h_rounds, void* stream);
+int ss_host_cluster_pairs(const uint32_t* h_pairs, uint64_t m, uint64_t n, const uint64_t* h_counts,
+                          const uint32_t* h_order, uint32_t method, uint32_t* h_rep, uint32_t* h_sizes, uint64_t* h_sums,
+                          uint64_t* h_nclusters);
 
 /* ------------------------------------------------------------------------------------------------
  * Dedup counter — replaces ShortSeqCounter._count_sequence (counter.pyx:41-54): key = (length,

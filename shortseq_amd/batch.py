@@ -31,7 +31,7 @@ __all__ = ["words_for", "wpr_for", "encode", "encode_var", "decode", "decode_var
            "hamming_pair", "encode_hamming_ref", "synth_reads", "synth_pool_reads", "synth_zipf_reads", "zipf_cdf",
            "GpuCounter",
            "raise_read_error", "first_bad_buffer", "fastq_index", "gather_rows", "slice_fixed",
-           "slice_var", "hamming_all_pairs", "HostStager", "host_stager", "encode_host", "decode_host"]
+           "slice_var", "hamming_all_pairs", "cluster_pairs", "umi_cluster", "HostStager", "host_stager", "encode_host", "decode_host"]
 
 
 def words_for(L: int) -> int:
@@ -638,6 +638,76 @@ def hamming_all_pairs(words: torch.Tensor, L: int, max_dist: int, *, counts: boo
         key = p[:, 0] * (1 << 32) + p[:, 1]
         pairs = pairs[:m][torch.argsort(key)]
     return cnt, pairs, total
+
+
+CLUSTER_METHODS = {"cluster": 0, "directional": 1}
+
+
+def cluster_pairs(pairs: torch.Tensor, n: int, counts: Optional[torch.Tensor] = None, method: str = "directional",
+                  want_sums: bool = True):
+    """Group n nodes (distinct UMIs) by an undirected pair list, as UMI-tools' `cluster` (connected
+    components) or `directional` (edge u -> v iff c[u] >= 2 c[v] - 1) method (ss_cluster_pairs; the
+    `adjacency` method, a sequential greedy cover, is not provided).  pairs: int32 [m, 2] on the
+    device, i < j, any order (hamming_all_pairs' pair output); counts: int64 [n] or None (required for
+    "directional").  -> (rep int64 [n]: every node's representative, reps int64 [k]: the
+    representatives by count descending, ties by index, sizes int64 [k], sums int64 [k] of the
+    clusters' counts or None, rounds).  The stable descending sort of the counts is a torch call;
+    the grouping runs in the HIP kernels.  Synchronises with the current stream once per round."""
+    _require_cuda(pairs, "pairs")
+    if pairs.dtype != torch.int32 or pairs.dim() != 2 or pairs.shape[1] != 2:
+        raise TypeError("pairs must be an int32 [m, 2] tensor")
+    dev = pairs.device
+    m = pairs.shape[0]
+    order = None
+    if counts is not None:
+        _require_cuda(counts, "counts")
+        if counts.dtype != torch.int64 or counts.numel() != n:
+            raise TypeError("counts must be an int64 [n] tensor")
+        order = torch.sort(counts, descending=True, stable=True).indices.to(torch.int32)
+    sums_on = want_sums and counts is not None
+    L_ = lib()
+    ws_bytes = int(L_.ss_cluster_ws_bytes(n, m))
+    ws = torch.empty((ws_bytes + 7) // 8, dtype=torch.int64, device=dev)
+    rep = torch.empty(n, dtype=torch.int32, device=dev)
+    sizes = torch.empty(n, dtype=torch.int32, device=dev)
+    sums = torch.empty(n, dtype=torch.int64, device=dev) if sums_on else None
+    ncl = torch.empty(1, dtype=torch.int64, device=dev)
+    rounds = C.c_uint32(0)
+    check(L_.ss_cluster_pairs(pairs.data_ptr(), m, n, _ptr(counts), _ptr(order), CLUSTER_METHODS[method], ws.data_ptr(),
+                              ws_bytes, rep.data_ptr(), sizes.data_ptr(), _ptr(sums), ncl.data_ptr(), C.byref(rounds),
+                              _stream(dev)), "ss_cluster_pairs")
+    rep = rep.to(torch.int64) & 0xFFFFFFFF
+    ids = torch.arange(n, dtype=torch.int64, device=dev)
+    by_rank = ids if order is None else order.to(torch.int64) & 0xFFFFFFFF
+    reps = by_rank[rep[by_rank] == by_rank]
+    if reps.numel() != int(ncl.item()):
+        raise AssertionError("ss_cluster_pairs: cluster count and representatives disagree")
+    return (rep, reps, sizes[reps].to(torch.int64) & 0xFFFFFFFF, sums[reps] if sums_on else None, int(rounds.value))
+
+
+def umi_cluster(words: torch.Tensor, L: int, max_dist: int, counts: Optional[torch.Tensor] = None,
+                method: str = "directional", pair_method: str = "auto", max_pairs_hint: Optional[int] = None):
+    """UMI dedup of n distinct packed reads on the device: the pairs within `max_dist`
+    (ss_hamming_all_pairs_ex, no neighbour counts, a pair buffer of max_pairs_hint -- default 4 n --
+    and one more run with exactly the total when that was too small), then cluster_pairs.
+    -> cluster_pairs' tuple plus the pair total."""
+    _require_cuda(words, "words")
+    n, wpr = words.shape
+    dev = words.device
+    cap = max(1, 4 * n if max_pairs_hint is None else max_pairs_hint)
+    tot = torch.empty(1, dtype=torch.int64, device=dev)
+    if n < 2:           # no pair to look for
+        return cluster_pairs(torch.empty((0, 2), dtype=torch.int32, device=dev), n, counts, method) + (0,)
+    while True:
+        pairs = torch.empty((cap, 2), dtype=torch.int32, device=dev)
+        check(lib().ss_hamming_all_pairs_ex(words.data_ptr(), n, L, wpr, max_dist, None, pairs.data_ptr(), cap,
+                                            tot.data_ptr(), ALL_PAIRS_METHODS[pair_method], _stream(dev)),
+              "ss_hamming_all_pairs_ex")
+        total = int(tot.item())
+        if total <= cap:
+            break
+        cap = total
+    return cluster_pairs(pairs[:total], n, counts, method) + (total,)
 
 
 LEN_UNDERFLOW = 0xFFFFFFFF   # ss_fastq_index: strlen 0 (the reference's size_t underflow -> too long)
