@@ -186,6 +186,56 @@ int ss_hamming_all_pairs_ex(const uint64_t* d_words, uint64_t n, uint32_t L, uin
                             uint32_t method, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Nearest-reference hamming match: every query row against a SECOND set of rows (barcode correction
+ * against a whitelist, demultiplexing against sample indices, guide / feature barcodes; new in this
+ * ABI version, replaces no reference interface).
+ * Inputs: nq packed query rows (stride q_wpr words) and nr packed reference rows (stride r_wpr words)
+ * of one length L, 1 .. 1024; nq < 2^32, nr < 2^32.
+ * Distance: exactly that of ss_hamming_all_pairs, the reference __xor__ over W = (L <= 32 ? 1 :
+ * ceil(L/32)) whole words, so position L of a one-word row (the table-path alias bit) counts.  Words
+ * W .. wpr-1 of either side are never read.
+ * Outputs per query i (u32 each):
+ *   d_dist[i]   the minimum distance to any reference if it is <= max_dist, else SS_NEAREST_NONE;
+ *   d_idx[i]    the LOWEST reference index at that minimum distance, else SS_NEAREST_NONE;
+ *   d_nbest[i]  (nullable) how many references lie at that minimum distance, 0 when none: duplicated
+ *               whitelist entries and equidistant neighbours both show here, and a caller corrects a
+ *               barcode only when it is 1.
+ * max_dist is any u32 (at or above the number of compared positions every reference qualifies: the
+ * outputs are the true nearest).  nr == 0 gives "none" for every query; nq == 0 is a no-op, SS_OK.
+ * The results do not depend on the launch geometry, on ref_splits or on run order: every merge step
+ * carries (distance, lowest index, count) and the rule -- the lower distance wins, equal distances
+ * add their counts and keep the lower index -- is associative and commutative.
+ * The device entry points keep the plain contract (asynchronous on `stream`, no allocation, no
+ * synchronisation, no host read-back, capturable); a size past one launch's grid is split into
+ * several launches inside the call.  The caller supplies d_ws (4-B aligned) of
+ * ss_hamming_nearest_ws_bytes(nq, nr, L, ref_splits) bytes, with the same ref_splits as the call
+ * (ss_hamming_nearest: 0); that is 0 bytes, and d_ws may be NULL, when one reference range is used.
+ * Kernels: L <= 128 the one-hot MFMA tiles of the all-pairs form on a rectangular grid, a block of
+ * 1024 / 512 / 256 / 128 query rows for min(L + 1, 32 W) <= 16 / 24 / 32 / 128 compared positions;
+ * above 128 nt bit-plane tiles, 256 rows per block.  ref_splits (_ex; a test hook) cuts the
+ * references into that many contiguous ranges of whole 32-row blocks, one partial result per (range,
+ * query) in the workspace, merged in range order by a finishing kernel; a value above ceil(nr / 32)
+ * (or 1024) is clamped, ranges are never empty; 0 chooses (more ranges when nq alone gives too few
+ * blocks for the device).
+ * SS_EARG: a NULL required pointer (nq > 0: d_q, d_idx, d_dist; d_ref when nr > 0), L out of range,
+ * q_wpr or r_wpr below W, a workspace that is too small, nq or nr >= 2^32; nothing is written.
+ * ss_host_hamming_nearest: the same function in plain C++ on host arrays (a loop over
+ * ss_host_hamming's word rule), for small inputs and hosts without a GPU; the same SS_EARG cases,
+ * checked before anything is written.
+ * ---------------------------------------------------------------------------------------------- */
+#define SS_NEAREST_NONE 0xFFFFFFFFu
+uint64_t ss_hamming_nearest_ws_bytes(uint64_t nq, uint64_t nr, uint32_t L, uint32_t ref_splits);
+int ss_hamming_nearest(const uint64_t* d_q, uint64_t nq, uint32_t q_wpr, const uint64_t* d_ref, uint64_t nr,
+                       uint32_t r_wpr, uint32_t L, uint32_t max_dist, uint32_t* d_idx, uint32_t* d_dist, uint32_t* d_nbest,
+                       void* d_ws, uint64_t ws_bytes, void* stream);
+int ss_hamming_nearest_ex(const uint64_t* d_q, uint64_t nq, uint32_t q_wpr, const uint64_t* d_ref, uint64_t nr,
+                          uint32_t r_wpr, uint32_t L, uint32_t max_dist, uint32_t* d_idx, uint32_t* d_dist,
+                          uint32_t* d_nbest, void* d_ws, uint64_t ws_bytes, uint32_t ref_splits, void* stream);
+int ss_host_hamming_nearest(const uint64_t* h_q, uint64_t nq, uint32_t q_wpr, const uint64_t* h_ref, uint64_t nr,
+                            uint32_t r_wpr, uint32_t L, uint32_t max_dist, uint32_t* h_idx, uint32_t* h_dist,
+                            uint32_t* h_nbest);
+
+/* ------------------------------------------------------------------------------------------------
  * UMI clustering over a pair list (the step after ss_hamming_all_pairs* in a UMI dedup; new in this ABI
  * version, replaces no reference interface — the reference's shortseq/umi/ package is unfinished).
  * n < 2^32 nodes (distinct UMIs), m undirected pairs (i, j) as two u32 each (any order, duplicates

@@ -80,6 +80,10 @@ SIGNATURES = [
     ("ss_slice_var", C.c_int, [_P, _U64, _U32, _P, _P, _P, _P, _U32, _P]),
     ("ss_hamming_all_pairs", C.c_int, [_P, _U64, _U32, _U32, _U32, _P, _P, _U64, _P, _P]),
     ("ss_hamming_all_pairs_ex", C.c_int, [_P, _U64, _U32, _U32, _U32, _P, _P, _U64, _P, _U32, _P]),
+    ("ss_hamming_nearest_ws_bytes", _U64, [_U64, _U64, _U32, _U32]),
+    ("ss_hamming_nearest", C.c_int, [_P, _U64, _U32, _P, _U64, _U32, _U32, _U32, _P, _P, _P, _P, _U64, _P]),
+    ("ss_hamming_nearest_ex", C.c_int, [_P, _U64, _U32, _P, _U64, _U32, _U32, _U32, _P, _P, _P, _P, _U64, _U32, _P]),
+    ("ss_host_hamming_nearest", C.c_int, [_P, _U64, _U32, _P, _U64, _U32, _U32, _U32, _P, _P, _P]),
     ("ss_cluster_ws_bytes", _U64, [_U64, _U64]),
     ("ss_cluster_pairs", C.c_int, [_P, _U64, _U64, _P, _P, _U32, _P, _U64, _P, _P, _P, _P, C.POINTER(C.c_uint32), _P]),
     ("ss_host_cluster_pairs", C.c_int, [_P, _U64, _U64, _P, _P, _U32, _P, _P, _P, _P]),

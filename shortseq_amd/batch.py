@@ -31,7 +31,7 @@ __all__ = ["words_for", "wpr_for", "encode", "encode_var", "decode", "decode_var
            "hamming_pair", "encode_hamming_ref", "synth_reads", "synth_pool_reads", "synth_zipf_reads", "zipf_cdf",
            "GpuCounter",
            "raise_read_error", "first_bad_buffer", "fastq_index", "gather_rows", "slice_fixed",
-           "slice_var", "hamming_all_pairs", "cluster_pairs", "umi_cluster", "HostStager", "host_stager", "encode_host", "decode_host"]
+           "slice_var", "hamming_all_pairs", "hamming_nearest", "cluster_pairs", "umi_cluster", "HostStager", "host_stager", "encode_host", "decode_host"]
 
 
 def words_for(L: int) -> int:
@@ -638,6 +638,38 @@ def hamming_all_pairs(words: torch.Tensor, L: int, max_dist: int, *, counts: boo
         key = p[:, 0] * (1 << 32) + p[:, 1]
         pairs = pairs[:m][torch.argsort(key)]
     return cnt, pairs, total
+
+
+def hamming_nearest(queries: torch.Tensor, refs: torch.Tensor, L: int, max_dist: int, *, want_nbest: bool = True,
+                    ref_splits: int = 0):
+    """Every query row against a second set of rows (barcodes against a whitelist; ss_hamming_nearest_ex):
+    queries int64 [nq, q_wpr], refs int64 [nr, r_wpr] on one device, one length L.  -> (idx, dist, nbest)
+    int64 [nq]: the lowest reference index at the minimum distance, that distance, and how many
+    references lie at it; idx = dist = -1 (nbest 0) where no reference is within max_dist.  nbest is
+    None when not wanted.  ref_splits: 0 lets the library cut the references into ranges, n forces n
+    (clamped to the 32-row blocks of refs); the results are the same.  Allocates the workspace, runs on
+    the current stream, makes no host sync of its own."""
+    _require_cuda(queries, "queries")
+    _require_cuda(refs, "refs")
+    if queries.dtype != torch.int64 or refs.dtype != torch.int64 or queries.dim() != 2 or refs.dim() != 2:
+        raise TypeError("queries and refs must be int64 [n, wpr] tensors")
+    if refs.device != queries.device:
+        raise ValueError("queries and refs must be on one device")
+    dev = queries.device
+    (nq, q_wpr), (nr, r_wpr) = queries.shape, refs.shape
+    L_ = lib()
+    ws_bytes = int(L_.ss_hamming_nearest_ws_bytes(nq, nr, L, ref_splits))
+    ws = torch.empty((ws_bytes + 3) // 4, dtype=torch.int32, device=dev) if ws_bytes else None
+    idx = torch.empty(nq, dtype=torch.int32, device=dev)
+    dist = torch.empty(nq, dtype=torch.int32, device=dev)
+    nbest = torch.empty(nq, dtype=torch.int32, device=dev) if want_nbest else None
+    check(L_.ss_hamming_nearest_ex(queries.data_ptr(), nq, q_wpr, refs.data_ptr(), nr, r_wpr, L, max_dist,
+                                   idx.data_ptr(), dist.data_ptr(), _ptr(nbest), _ptr(ws), ws_bytes, ref_splits,
+                                   _stream(dev)), "ss_hamming_nearest_ex")
+    def widen(t, none_to_minus1):     # u32 held in int32 -> int64; SS_NEAREST_NONE (0xFFFFFFFF) -> -1
+        u = t.to(torch.int64) & 0xFFFFFFFF
+        return torch.where(u == 0xFFFFFFFF, torch.full_like(u, -1), u) if none_to_minus1 else u
+    return widen(idx, True), widen(dist, True), None if nbest is None else widen(nbest, False)
 
 
 CLUSTER_METHODS = {"cluster": 0, "directional": 1}

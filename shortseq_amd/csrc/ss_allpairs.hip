@@ -24,17 +24,6 @@ namespace {
 
 using namespace ssd;
 
-// even bits of x (nt codes' low bits) -> 32-bit plane; odd bits -> the other plane
-__device__ __forceinline__ uint32_t even_bits(uint64_t x) {
-    x &= 0x5555555555555555ull;
-    x = (x | (x >> 1)) & 0x3333333333333333ull;
-    x = (x | (x >> 2)) & 0x0F0F0F0F0F0F0F0Full;
-    x = (x | (x >> 4)) & 0x00FF00FF00FF00FFull;
-    x = (x | (x >> 8)) & 0x0000FFFF0000FFFFull;
-    x = (x | (x >> 16)) & 0x00000000FFFFFFFFull;
-    return (uint32_t)x;
-}
-
 struct AllPairsArgs {
     const uint64_t* words;
     uint64_t n;
@@ -173,10 +162,8 @@ __global__ __launch_bounds__(256) void k_allpairs(AllPairsArgs a) {
 // OR-reduced (bits 7-8 after a 128 - thr bias) and tested with one ballot, so the (rare) hit path runs
 // only for tiles that have one.
 // Rows / columns past n get zero fragments (D = 0); the hit path checks indices.
+// (v4i32 / v16i32 and the table form of the fragments live in ss_device.h: ss_nearest.hip shares them.)
 // ------------------------------------------------------------------------------------------------
-typedef int v4i32 __attribute__((ext_vector_type(4)));
-typedef int v16i32 __attribute__((ext_vector_type(16)));
-
 template <int KS>
 __device__ __forceinline__ void onehot_frag(uint64_t word, bool valid, uint32_t P, uint32_t h, v4i32* f) {
 #pragma unroll
@@ -264,12 +251,7 @@ __global__ __launch_bounds__(256) void k_allpairs_mfma(AllPairsArgs a, uint32_t 
     if (threadIdx.x == 0) blkhits = 0;
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, h = lane >> 5, r = lane & 31u;
     const uint64_t row0 = (uint64_t)bi * S, col0 = (uint64_t)bj * S;
-    if (TAB) {
-        v4i32 e;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) e[q] = (int)(1u << (8u * ((threadIdx.x >> (2 * q)) & 3u)));
-        ohtab[threadIdx.x] = e;
-    }
+    if (TAB) ohtab[threadIdx.x] = onehot_entry(threadIdx.x);
     for (int c = threadIdx.x; c < S; c += 256) {
         const uint64_t j = col0 + c;
 #pragma unroll
@@ -281,12 +263,7 @@ __global__ __launch_bounds__(256) void k_allpairs_mfma(AllPairsArgs a, uint32_t 
     // k-step s covers positions 8s .. 8s+7 = byte 2(s % 4) + h of word s / 4 (4 codes per byte)
     auto frag = [&](const uint64_t* word, bool valid, v4i32* f) {
         if constexpr (TAB) {
-#pragma unroll
-            for (int s2 = 0; s2 < KS; ++s2) {
-                const v4i32 z = {0, 0, 0, 0};
-                const uint32_t byte = (uint32_t)(word[s2 / 4] >> (16 * (s2 % 4) + 8 * h)) & 0xFFu;
-                f[s2] = valid ? ohtab[byte] : z;
-            }
+            onehot_frag_tab<KS>(ohtab, word, valid, h, f);
         } else {
             static_assert(TAB || NW == 1, "the arithmetic one-hot build is one-word only");
             onehot_frag<KS>(word[0], valid, P, h, f);
