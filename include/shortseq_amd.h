@@ -186,6 +186,57 @@ int ss_hamming_all_pairs_ex(const uint64_t* d_words, uint64_t n, uint32_t L, uin
                             uint32_t method, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Grouped all-pairs thresholded hamming: ss_hamming_all_pairs restricted to groups (UMI dedup per cell
+ * barcode x gene, or per mapping position: UMIs are only comparable inside one group, and a sample has
+ * 10^5 - 10^7 groups, most of 1 - 20 rows; new in this ABI version, replaces no reference interface).
+ * Rows: n < 2^32 packed rows of one length L, 1 .. 1024, at stride wpr >= W, sorted by group.
+ * Groups: group g is rows [off[g], off[g + 1]); off has ngroups + 1 u32 entries, is nondecreasing,
+ * off[0] = 0 and off[ngroups] = n.  Empty groups are allowed; ngroups == 0 requires n == 0.
+ * Distance: exactly that of ss_hamming_all_pairs, the reference __xor__ over W = (L <= 32 ? 1 :
+ * ceil(L/32)) whole words, so position L of a one-word row (the table-path alias bit) counts.  Words
+ * W .. wpr-1 are never read.
+ * Outputs (as ss_hamming_all_pairs): the entry point zeroes d_counts and *d_npairs; every unordered pair
+ * i < j OF ONE GROUP within max_dist adds 1 to d_counts[i] and d_counts[j] (nullable) and is appended as
+ * two u32 GLOBAL row indices to d_pairs (nullable; max_pairs == 0 also means none) while fewer than
+ * max_pairs were written; *d_npairs = all such pairs (may exceed max_pairs).  Pair order is unspecified
+ * (each pair is written as i < j).  max_dist is any u32.  The indices being global, ss_cluster_pairs runs
+ * on the result as it stands: a pair list that never crosses a group gives clusters inside groups, and
+ * its representative is the one a per-group run would choose ("Grouped all-pairs").
+ * The device entry points keep the plain contract (asynchronous on `stream`, no allocation, no
+ * synchronisation, no host read-back, capturable).  The caller supplies d_ws (8-B aligned) of
+ * ss_hamming_all_pairs_grouped_ws_bytes(n, ngroups, L) bytes; this implementation needs none: the
+ * function returns 0, d_ws may be NULL and no ws_bytes is too small.
+ * Kernel: one block of 256 threads per row tile of 256 consecutive rows, whatever the groups are; a
+ * lane owns a row (bit planes in registers) and finds its group's end by a binary search over the
+ * offsets; the block walks column chunks from its own tile to its last row's group end, each wave only
+ * over [its first row + 1, its last row's group end).  Every pair of a group is checked (bit-plane
+ * VALU form at every L): no MFMA tiles and no pigeonhole form inside groups -- for ONE group of 10^5 or
+ * more rows ss_hamming_all_pairs is the tool.  Also not provided: UMI-tools' `adjacency` method and a
+ * grouped form of the whitelist match (ss_hamming_nearest).  tiles_per_launch (_ex; a test hook): row tiles per
+ * kernel launch, 0 = the library's 2^23 (larger values are clamped to it); the results do not depend on it.
+ * Malformed offsets are NOT detected on the device: the kernel still never reads or writes outside the
+ * arrays (every end is clamped to n, an end <= i means "no partners", no index >= n is written to
+ * d_pairs); the outputs are then unspecified.
+ * SS_EARG (nothing is written): a NULL required pointer (n > 0: d_words, d_group_offsets, d_npairs), L
+ * out of range, wpr < W, n >= 2^32, ngroups == 0 with n > 0, a workspace that is too small.
+ * ss_host_hamming_all_pairs_grouped: the same function in plain C++ on host arrays over
+ * ss_host_hamming's word rule, pairs in ascending (i, j) order; it DOES validate the offsets:
+ * off[0] != 0, a decrease, or off[ngroups] != n is SS_EARG, checked before anything is written.
+ * ---------------------------------------------------------------------------------------------- */
+uint64_t ss_hamming_all_pairs_grouped_ws_bytes(uint64_t n, uint64_t ngroups, uint32_t L);
+int ss_hamming_all_pairs_grouped(const uint64_t* d_words, uint64_t n, uint32_t L, uint32_t wpr, uint32_t max_dist,
+                                 const uint32_t* d_group_offsets, uint64_t ngroups,
+                                 uint32_t* d_counts, uint32_t* d_pairs, uint64_t max_pairs, uint64_t* d_npairs,
+                                 void* d_ws, uint64_t ws_bytes, void* stream);
+int ss_hamming_all_pairs_grouped_ex(const uint64_t* d_words, uint64_t n, uint32_t L, uint32_t wpr, uint32_t max_dist,
+                                    const uint32_t* d_group_offsets, uint64_t ngroups,
+                                    uint32_t* d_counts, uint32_t* d_pairs, uint64_t max_pairs, uint64_t* d_npairs,
+                                    void* d_ws, uint64_t ws_bytes, uint64_t tiles_per_launch, void* stream);
+int ss_host_hamming_all_pairs_grouped(const uint64_t* h_words, uint64_t n, uint32_t L, uint32_t wpr, uint32_t max_dist,
+                                      const uint32_t* h_group_offsets, uint64_t ngroups,
+                                      uint32_t* h_counts, uint32_t* h_pairs, uint64_t max_pairs, uint64_t* h_npairs);
+
+/* ------------------------------------------------------------------------------------------------
  * Nearest-reference hamming match: every query row against a SECOND set of rows (barcode correction
  * against a whitelist, demultiplexing against sample indices, guide / feature barcodes; new in this
  * ABI version, replaces no reference interface).

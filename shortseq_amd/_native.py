@@ -80,6 +80,11 @@ SIGNATURES = [
     ("ss_slice_var", C.c_int, [_P, _U64, _U32, _P, _P, _P, _P, _U32, _P]),
     ("ss_hamming_all_pairs", C.c_int, [_P, _U64, _U32, _U32, _U32, _P, _P, _U64, _P, _P]),
     ("ss_hamming_all_pairs_ex", C.c_int, [_P, _U64, _U32, _U32, _U32, _P, _P, _U64, _P, _U32, _P]),
+    ("ss_hamming_all_pairs_grouped_ws_bytes", _U64, [_U64, _U64, _U32]),
+    ("ss_hamming_all_pairs_grouped", C.c_int, [_P, _U64, _U32, _U32, _U32, _P, _U64, _P, _P, _U64, _P, _P, _U64, _P]),
+    ("ss_hamming_all_pairs_grouped_ex", C.c_int,
+     [_P, _U64, _U32, _U32, _U32, _P, _U64, _P, _P, _U64, _P, _P, _U64, _U64, _P]),
+    ("ss_host_hamming_all_pairs_grouped", C.c_int, [_P, _U64, _U32, _U32, _U32, _P, _U64, _P, _P, _U64, _P]),
     ("ss_hamming_nearest_ws_bytes", _U64, [_U64, _U64, _U32, _U32]),
     ("ss_hamming_nearest", C.c_int, [_P, _U64, _U32, _P, _U64, _U32, _U32, _U32, _P, _P, _P, _P, _U64, _P]),
     ("ss_hamming_nearest_ex", C.c_int, [_P, _U64, _U32, _P, _U64, _U32, _U32, _U32, _P, _P, _P, _P, _U64, _U32, _P]),

@@ -31,7 +31,8 @@ __all__ = ["words_for", "wpr_for", "encode", "encode_var", "decode", "decode_var
            "hamming_pair", "encode_hamming_ref", "synth_reads", "synth_pool_reads", "synth_zipf_reads", "zipf_cdf",
            "GpuCounter",
            "raise_read_error", "first_bad_buffer", "fastq_index", "gather_rows", "slice_fixed",
-           "slice_var", "hamming_all_pairs", "hamming_nearest", "cluster_pairs", "umi_cluster", "HostStager", "host_stager", "encode_host", "decode_host"]
+           "slice_var", "hamming_all_pairs", "hamming_nearest", "cluster_pairs", "umi_cluster",
+           "GROUPED_ROW_TILE", "hamming_all_pairs_grouped", "umi_cluster_grouped", "HostStager", "host_stager", "encode_host", "decode_host"]
 
 
 def words_for(L: int) -> int:
@@ -735,6 +736,97 @@ def umi_cluster(words: torch.Tensor, L: int, max_dist: int, counts: Optional[tor
         check(lib().ss_hamming_all_pairs_ex(words.data_ptr(), n, L, wpr, max_dist, None, pairs.data_ptr(), cap,
                                             tot.data_ptr(), ALL_PAIRS_METHODS[pair_method], _stream(dev)),
               "ss_hamming_all_pairs_ex")
+        total = int(tot.item())
+        if total <= cap:
+            break
+        cap = total
+    return cluster_pairs(pairs[:total], n, counts, method) + (total,)
+
+
+GROUPED_ROW_TILE = 256   # rows per block of k_gp_pairs (kGpTile, csrc/ss_grouped.hip)
+
+
+def _group_offsets(group_offsets, n: int, dev: torch.device) -> torch.Tensor:
+    """Group offsets (a device or host tensor, or a host sequence) -> the ABI's u32 [ngroups + 1] on
+    `dev`, held in an int32 tensor.  Checks first 0, nondecreasing, last n (one host read)."""
+    if isinstance(group_offsets, torch.Tensor):
+        if group_offsets.dtype not in (torch.int64, torch.int32):
+            raise TypeError("group_offsets must be an int64 or int32 tensor, or a host sequence")
+        off = group_offsets.reshape(-1).to(device=dev, dtype=torch.int64)
+    else:
+        off = torch.from_numpy(np.ascontiguousarray(group_offsets, dtype=np.int64).reshape(-1)).to(dev)
+    if n >= 1 << 32:
+        raise ValueError("n must be < 2^32")
+    if off.numel() == 0:
+        raise ValueError("group_offsets needs ngroups + 1 entries")
+    ok = (off[0] == 0) & (off[-1] == n) & (off[1:] >= off[:-1]).all()
+    if not bool(ok.item()):
+        raise ValueError("group_offsets must start at 0, never decrease, and end at the number of rows")
+    if off.numel() == 1 and n:
+        raise ValueError("rows without a group")
+    return torch.where(off >= 1 << 31, off - (1 << 32), off).to(torch.int32)      # u32 bits in int32
+
+
+def hamming_all_pairs_grouped(words: torch.Tensor, L: int, max_dist: int, group_offsets, *, counts: bool = True,
+                              max_pairs: int = 0):
+    """hamming_all_pairs restricted to groups: rows sorted by group, group g = rows
+    [group_offsets[g], group_offsets[g + 1]), only pairs inside one group are compared
+    (ss_hamming_all_pairs_grouped).  -> (neighbour counts int32 [n] or None, pairs int32 [m, 2] of
+    GLOBAL row indices or None, total pairs), shaped as hamming_all_pairs' result (pairs sorted, at most
+    max_pairs kept; 0: count only).  group_offsets: int64 / int32 tensor on the device or a host
+    sequence of ngroups + 1 entries; it is checked here (first 0, nondecreasing, last n: ValueError), which
+    reads one flag back from the device; the ABI call itself does not synchronise."""
+    _require_cuda(words, "words")
+    n, wpr = words.shape
+    dev = words.device
+    off = _group_offsets(group_offsets, n, dev)
+    L_ = lib()
+    ws_bytes = int(L_.ss_hamming_all_pairs_grouped_ws_bytes(n, off.numel() - 1, L))
+    ws = torch.empty((ws_bytes + 7) // 8, dtype=torch.int64, device=dev) if ws_bytes else None
+    cnt = torch.empty(n, dtype=torch.int32, device=dev) if counts else None
+    pairs = torch.empty((max(1, max_pairs), 2), dtype=torch.int32, device=dev) if max_pairs else None
+    tot = torch.empty(1, dtype=torch.int64, device=dev)
+    check(L_.ss_hamming_all_pairs_grouped(words.data_ptr(), n, L, wpr, max_dist, off.data_ptr(), off.numel() - 1,
+                                          _ptr(cnt), _ptr(pairs), max_pairs, tot.data_ptr(), _ptr(ws), ws_bytes,
+                                          _stream(dev)), "ss_hamming_all_pairs_grouped")
+    total = int(tot.item())
+    if pairs is not None:
+        m = min(total, max_pairs)
+        p = pairs[:m].to(torch.int64)
+        key = (p[:, 0] & 0xFFFFFFFF) * (1 << 32) + (p[:, 1] & 0xFFFFFFFF)
+        pairs = pairs[:m][torch.argsort(key)]
+    return cnt, pairs, total
+
+
+def umi_cluster_grouped(words: torch.Tensor, L: int, max_dist: int, group_offsets,
+                        counts: Optional[torch.Tensor] = None, method: str = "directional",
+                        max_pairs_hint: Optional[int] = None):
+    """UMI dedup of many groups (cell x gene, mapping position) in one call: the rows of all groups in
+    one batch, sorted by group, group_offsets as in hamming_all_pairs_grouped.  The pairs inside groups
+    (ss_hamming_all_pairs_grouped, no neighbour counts, a pair buffer of max_pairs_hint -- default 4 n --
+    and one more run with exactly the total when that was too small), then cluster_pairs on the global
+    indices: no pair crosses a group, so no cluster does, and rows of a group being contiguous, the
+    (count descending, index ascending) rank restricted to a group is the group's own, so every
+    representative is the one umi_cluster on that group alone would name.
+    -> cluster_pairs' tuple plus the pair total; all indices are global rows.  A cluster's group:
+    ``torch.bucketize(reps, offsets[1:], right=True)``."""
+    _require_cuda(words, "words")
+    n, wpr = words.shape
+    dev = words.device
+    off = _group_offsets(group_offsets, n, dev)
+    if n < 2:           # no pair to look for
+        return cluster_pairs(torch.empty((0, 2), dtype=torch.int32, device=dev), n, counts, method) + (0,)
+    L_ = lib()
+    ngroups = off.numel() - 1
+    ws_bytes = int(L_.ss_hamming_all_pairs_grouped_ws_bytes(n, ngroups, L))
+    ws = torch.empty((ws_bytes + 7) // 8, dtype=torch.int64, device=dev) if ws_bytes else None
+    cap = max(1, 4 * n if max_pairs_hint is None else max_pairs_hint)
+    tot = torch.empty(1, dtype=torch.int64, device=dev)
+    while True:
+        pairs = torch.empty((cap, 2), dtype=torch.int32, device=dev)
+        check(L_.ss_hamming_all_pairs_grouped(words.data_ptr(), n, L, wpr, max_dist, off.data_ptr(), ngroups, None,
+                                              pairs.data_ptr(), cap, tot.data_ptr(), _ptr(ws), ws_bytes, _stream(dev)),
+              "ss_hamming_all_pairs_grouped")
         total = int(tot.item())
         if total <= cap:
             break

@@ -44,17 +44,7 @@ struct Tile {
     static constexpr int C = C0 < S ? C0 : S;               // columns per LDS chunk (divides S)
 };
 
-template <int WT>
-__device__ __forceinline__ void load_planes(const AllPairsArgs& a, uint64_t r, uint32_t* lo, uint32_t* hi) {
-#pragma unroll
-    for (int w = 0; w < WT; ++w) {
-        uint64_t x = 0;
-        if (r < a.n && (uint32_t)w < a.W) x = a.words[r * a.wpr + w];
-        lo[w] = even_bits(x);
-        hi[w] = even_bits(x >> 1);
-    }
-}
-
+// (load_planes lives in ss_device.h: ss_grouped.hip shares it)
 template <int WT, int R>
 __global__ __launch_bounds__(256) void k_allpairs(AllPairsArgs a) {
     constexpr int S = Tile<WT, R>::S, C = Tile<WT, R>::C;
@@ -71,7 +61,7 @@ __global__ __launch_bounds__(256) void k_allpairs(AllPairsArgs a) {
 #pragma unroll
     for (int r = 0; r < R; ++r) {
         const uint64_t i = (uint64_t)bi * S + r * 256 + threadIdx.x;
-        load_planes<WT>(a, i, alo[r], ahi[r]);
+        load_planes<WT>(a.words, a.n, a.wpr, a.W, i, alo[r], ahi[r]);
         rowcnt[r] = 0;
     }
     const uint64_t nrow_lim = a.n;
@@ -81,7 +71,7 @@ __global__ __launch_bounds__(256) void k_allpairs(AllPairsArgs a) {
         __syncthreads();
         for (int c = threadIdx.x; c < C; c += 256) {
             uint32_t lo[WT], hi[WT];
-            load_planes<WT>(a, j0 + c, lo, hi);
+            load_planes<WT>(a.words, a.n, a.wpr, a.W, j0 + c, lo, hi);
 #pragma unroll
             for (int w = 0; w < WT; ++w) pl[c * WT + w] = make_uint2(lo[w], hi[w]);
             colcnt[c] = 0;
@@ -553,52 +543,9 @@ __global__ __launch_bounds__(256) void k_pig_scatter(PigArgs a) {
     }
 }
 
-// Hit output of a wave without one global atomic per hit ballot: pairs gather in a per-wave LDS
-// buffer and leave in runs (one pair-counter atomic per run of up to kPairBuf); count-only calls keep
-// the wave's hit count in a register and add it once.
-constexpr uint32_t kPairBuf = 512;
+// (WaveHits / hits_add / hits_flush, the per-wave LDS pair buffer, live in ss_device.h: ss_grouped.hip
+// shares them)
 constexpr uint64_t kPigTileWalk = 256;     // a wave's entry run past this: walked as broadcast tiles
-struct WaveHits {
-    uint2* buf;          // this wave's kPairBuf LDS entries
-    uint32_t fill = 0;   // wave-uniform
-    uint64_t nh = 0;     // wave-uniform (count-only)
-};
-__device__ __forceinline__ void lds_wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-template <typename A>
-__device__ __forceinline__ void hits_flush(const A& a, WaveHits& wh) {
-    if (!wh.fill) return;
-    lds_wave_sync();
-    const uint32_t lane = threadIdx.x & 63u;
-    unsigned long long base = 0;
-    if (lane == 0) base = atomicAdd(a.npairs, (unsigned long long)wh.fill);
-    base = __shfl(base, 0);
-    for (uint32_t e = lane; e < wh.fill; e += 64) {
-        const uint64_t slot = base + e;
-        if (slot < a.max_pairs) {
-            const uint2 pr = wh.buf[e];
-            a.pairs[2 * slot] = pr.x;
-            a.pairs[2 * slot + 1] = pr.y;
-        }
-    }
-    lds_wave_sync();
-    wh.fill = 0;
-}
-template <typename A>
-__device__ __forceinline__ void hits_add(const A& a, WaveHits& wh, bool hit, uint64_t mask, uint32_t i, uint32_t j) {
-    const uint32_t c = (uint32_t)__popcll(mask);
-    if (!a.pairs) {
-        wh.nh += c;
-        return;
-    }
-    if (wh.fill + c > kPairBuf) hits_flush(a, wh);
-    const uint32_t lane = threadIdx.x & 63u;
-    if (hit) wh.buf[wh.fill + __popcll(mask & ((1ull << lane) - 1ull))] = make_uint2(min(i, j), max(i, j));
-    wh.fill += c;
-}
 
 // one lane per read in bucket order of segment g = blockIdx.y, compared with the reads after it in its
 // bucket (see the walk below).  Hits leave through wave ballots into the wave's hit buffer; a

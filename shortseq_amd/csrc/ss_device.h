@@ -110,6 +110,67 @@ __device__ __forceinline__ uint32_t even_bits(uint64_t x) {
     return (uint32_t)x;
 }
 
+// {lo, hi} planes of the W compared words of row r of a packed batch (stride wpr); a row past n and the
+// words W .. WT-1 of the template are zero (k_allpairs, k_gp_pairs)
+template <int WT>
+__device__ __forceinline__ void load_planes(const uint64_t* words, uint64_t n, uint32_t wpr, uint32_t W, uint64_t r,
+                                            uint32_t* lo, uint32_t* hi) {
+#pragma unroll
+    for (int w = 0; w < WT; ++w) {
+        uint64_t x = 0;
+        if (r < n && (uint32_t)w < W) x = words[r * wpr + w];
+        lo[w] = even_bits(x);
+        hi[w] = even_bits(x >> 1);
+    }
+}
+
+// Hit output of a wave without one global atomic per hit ballot (the pigeonhole pair kernels of
+// ss_allpairs.hip, k_gp_pairs): pairs gather in a per-wave LDS buffer and leave in runs (one
+// pair-counter atomic per run of up to kPairBuf); count-only calls keep the wave's hit count in a
+// register and add it once.  A: any argument struct with pairs, max_pairs and npairs.
+constexpr uint32_t kPairBuf = 512;
+struct WaveHits {
+    uint2* buf;          // this wave's kPairBuf LDS entries
+    uint32_t fill = 0;   // wave-uniform
+    uint64_t nh = 0;     // wave-uniform (count-only)
+};
+__device__ __forceinline__ void lds_wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+template <typename A>
+__device__ __forceinline__ void hits_flush(const A& a, WaveHits& wh) {
+    if (!wh.fill) return;
+    lds_wave_sync();
+    const uint32_t lane = threadIdx.x & 63u;
+    unsigned long long base = 0;
+    if (lane == 0) base = atomicAdd(a.npairs, (unsigned long long)wh.fill);
+    base = __shfl(base, 0);
+    for (uint32_t e = lane; e < wh.fill; e += 64) {
+        const uint64_t slot = base + e;
+        if (slot < a.max_pairs) {
+            const uint2 pr = wh.buf[e];
+            a.pairs[2 * slot] = pr.x;
+            a.pairs[2 * slot + 1] = pr.y;
+        }
+    }
+    lds_wave_sync();
+    wh.fill = 0;
+}
+template <typename A>
+__device__ __forceinline__ void hits_add(const A& a, WaveHits& wh, bool hit, uint64_t mask, uint32_t i, uint32_t j) {
+    const uint32_t c = (uint32_t)__popcll(mask);
+    if (!a.pairs) {
+        wh.nh += c;
+        return;
+    }
+    if (wh.fill + c > kPairBuf) hits_flush(a, wh);
+    const uint32_t lane = threadIdx.x & 63u;
+    if (hit) wh.buf[wh.fill + __popcll(mask & ((1ull << lane) - 1ull))] = make_uint2(min(i, j), max(i, j));
+    wh.fill += c;
+}
+
 // One-hot i8 fragments of v_mfma_i32_32x32x32_i8 for the hamming tiles (ss_allpairs.hip's header
 // has the scheme): position p of a read -> 4 int8 lanes with a 1 at its code.  A 256-entry LDS
 // table maps the 4 codes of a byte to the 4 one-hot VGPRs of a k-step half (one ds_read_b128):
