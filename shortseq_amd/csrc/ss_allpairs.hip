@@ -9,7 +9,7 @@
 // (32 nt) is split once into two bit-planes (lo = even bits, hi = odd bits, 32 bits each), so a
 // pair costs, per word: lo_a^lo_b, hi_a^hi_b, OR, v_bcnt (accumulating) — then one compare and
 // one add for the row count: ~6 VALU ops per pair per word instead of ~10 on the interleaved form.
-// Tiling: a block owns a row tile of S = 256 * R reads held in registers (R per lane, converted to
+// Tiling: a block owns a row tile of S = 256 reads held in registers (one per lane, converted to
 // planes on load) and a column tile of S reads, staged through LDS in chunks (planes), read by
 // every lane with broadcast LDS reads.  Only tile pairs bj >= bi run (unordered pairs once; the
 // diagonal tile masks j <= i).  Hits are rare for UMI thresholds, so they leave the inner loop
@@ -17,7 +17,7 @@
 // are appended with one global atomic per wave.
 #include <mutex>
 
-#include "ss_device.h"
+#include "ss_hamming.h"
 #include "ss_internal.h"
 
 namespace {
@@ -28,26 +28,24 @@ struct AllPairsArgs {
     const uint64_t* words;
     uint64_t n;
     uint32_t wpr;       // words per read in memory
-    uint32_t W;         // words compared (ham_words(L)); words W..WT-1 of the template are zero
+    uint32_t W;         // words compared (ham_shape(L).W); words W..WT-1 of the template are zero
     uint32_t k;         // max distance
-    uint32_t ntiles;
     uint32_t* counts;   // nullable
     uint32_t* pairs;    // nullable: (i, j) u32 pairs
     uint64_t max_pairs;
     unsigned long long* npairs;
 };
 
-template <int WT, int R>
+template <int WT>
 struct Tile {
-    static constexpr int S = 256 * R;                        // reads per tile
+    static constexpr int S = 256;                            // reads per tile: one per lane
     static constexpr int C0 = (WT <= 4) ? 1024 : (4096 / WT);
     static constexpr int C = C0 < S ? C0 : S;               // columns per LDS chunk (divides S)
 };
 
-// (load_planes lives in ss_device.h: ss_grouped.hip shares it)
-template <int WT, int R>
+template <int WT>
 __global__ __launch_bounds__(256) void k_allpairs(AllPairsArgs a) {
-    constexpr int S = Tile<WT, R>::S, C = Tile<WT, R>::C;
+    constexpr int S = Tile<WT>::S, C = Tile<WT>::C;
     const uint32_t bi = blockIdx.y, bj = blockIdx.x;
     if (bj < bi) return;                                    // unordered pairs: upper triangle only
     __shared__ uint2 pl[C * WT];                             // {lo, hi} planes per column word
@@ -55,16 +53,18 @@ __global__ __launch_bounds__(256) void k_allpairs(AllPairsArgs a) {
     __shared__ unsigned long long blkhits;   // count-only calls: the block's hits, one global atomic
     if (threadIdx.x == 0) blkhits = 0;
     const bool diag = bi == bj;
-    // rows of this lane: i = bi*S + r*256 + tid
-    uint32_t alo[R][WT], ahi[R][WT];
-    uint32_t rowcnt[R];
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        const uint64_t i = (uint64_t)bi * S + r * 256 + threadIdx.x;
-        load_planes<WT>(a.words, a.n, a.wpr, a.W, i, alo[r], ahi[r]);
-        rowcnt[r] = 0;
+    uint32_t alo[WT], ahi[WT];
+    {
+        const uint64_t i = (uint64_t)bi * S + threadIdx.x;     // this lane's row
+        load_planes<WT>(a.words, a.n, a.wpr, a.W, i, alo, ahi);
     }
-    const uint64_t nrow_lim = a.n;
+    uint32_t rowcnt = 0;
+    // WT <= 16: one chunk (C == S), and the loop is unrolled away (a count past the trip count is a
+    // full unroll; left to itself the compiler keeps the loop, at 8 .. 12 VGPRs).  WT 32: two chunks, a loop.
+    // (The chunk as a lambda under `if constexpr (C == S)`, with i defined once, measured 7 .. 12 % slower
+    // at 150, 250 and 1024 nt: profiles/hamming_refactor.)
+    constexpr int kChunkUnroll = C == S ? 2 : 1;
+#pragma unroll kChunkUnroll
     for (int c0 = 0; c0 < S; c0 += C) {
         const uint64_t j0 = (uint64_t)bj * S + c0;
         if (j0 >= a.n) break;
@@ -88,35 +88,32 @@ __global__ __launch_bounds__(256) void k_allpairs(AllPairsArgs a) {
                 bhi[w] = p.y;
             }
             const uint64_t j = j0 + c;
+            const uint64_t i = (uint64_t)bi * S + threadIdx.x;
+            uint32_t d = 0;
 #pragma unroll
-            for (int r = 0; r < R; ++r) {
-                const uint64_t i = (uint64_t)bi * S + r * 256 + threadIdx.x;
-                uint32_t d = 0;
-#pragma unroll
-                for (int w = 0; w < WT; ++w) d += __popc((alo[r][w] ^ blo[w]) | (ahi[r][w] ^ bhi[w]));
-                bool hit = d <= a.k && i < nrow_lim;
-                if (diag) hit = hit && j > i;
-                rowcnt[r] += hit ? 1u : 0u;
-                if (__ballot(hit)) {                        // rare: column count + pair output
-                    if (hit && a.counts) atomicAdd(&colcnt[c], 1u);
-                    if (a.pairs) {
-                        const uint64_t mask = __ballot(hit);
-                        const uint32_t lane = threadIdx.x & 63u;
-                        const uint32_t rank = __popcll(mask & ((1ull << lane) - 1ull));
-                        unsigned long long base = 0;
-                        if (lane == (uint32_t)__ffsll((unsigned long long)mask) - 1u)
-                            base = atomicAdd(a.npairs, (unsigned long long)__popcll(mask));
-                        base = __shfl(base, __ffsll((unsigned long long)mask) - 1);
-                        const uint64_t slot = base + rank;
-                        if (hit && slot < a.max_pairs) {
-                            a.pairs[2 * slot] = (uint32_t)i;
-                            a.pairs[2 * slot + 1] = (uint32_t)j;
-                        }
-                    } else {
-                        const uint64_t mask = __ballot(hit);   // all lanes, before the leader's branch
-                        if ((threadIdx.x & 63u) == (uint32_t)__ffsll((unsigned long long)mask) - 1u)
-                            atomicAdd(&blkhits, (unsigned long long)__popcll(mask));
+            for (int w = 0; w < WT; ++w) d += __popc((alo[w] ^ blo[w]) | (ahi[w] ^ bhi[w]));
+            bool hit = d <= a.k && i < a.n;
+            if (diag) hit = hit && j > i;
+            rowcnt += hit ? 1u : 0u;
+            if (__ballot(hit)) {                            // rare: column count + pair output
+                if (hit && a.counts) atomicAdd(&colcnt[c], 1u);
+                if (a.pairs) {
+                    const uint64_t mask = __ballot(hit);
+                    const uint32_t lane = threadIdx.x & 63u;
+                    const uint32_t rank = __popcll(mask & ((1ull << lane) - 1ull));
+                    unsigned long long base = 0;
+                    if (lane == (uint32_t)__ffsll((unsigned long long)mask) - 1u)
+                        base = atomicAdd(a.npairs, (unsigned long long)__popcll(mask));
+                    base = __shfl(base, __ffsll((unsigned long long)mask) - 1);
+                    const uint64_t slot = base + rank;
+                    if (hit && slot < a.max_pairs) {
+                        a.pairs[2 * slot] = (uint32_t)i;
+                        a.pairs[2 * slot + 1] = (uint32_t)j;
                     }
+                } else {
+                    const uint64_t mask = __ballot(hit);   // all lanes, before the leader's branch
+                    if ((threadIdx.x & 63u) == (uint32_t)__ffsll((unsigned long long)mask) - 1u)
+                        atomicAdd(&blkhits, (unsigned long long)__popcll(mask));
                 }
             }
         }
@@ -128,13 +125,8 @@ __global__ __launch_bounds__(256) void k_allpairs(AllPairsArgs a) {
     }
     __syncthreads();
     if (threadIdx.x == 0 && blkhits) atomicAdd(a.npairs, blkhits);
-    if (a.counts) {
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            const uint64_t i = (uint64_t)bi * S + r * 256 + threadIdx.x;
-            if (i < a.n && rowcnt[r]) atomicAdd(&a.counts[i], rowcnt[r]);
-        }
-    }
+    const uint64_t i = (uint64_t)bi * S + threadIdx.x;
+    if (a.counts && i < a.n && rowcnt) atomicAdd(&a.counts[i], rowcnt);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -152,23 +144,11 @@ __global__ __launch_bounds__(256) void k_allpairs(AllPairsArgs a) {
 // OR-reduced (bits 7-8 after a 128 - thr bias) and tested with one ballot, so the (rare) hit path runs
 // only for tiles that have one.
 // Rows / columns past n get zero fragments (D = 0); the hit path checks indices.
-// (v4i32 / v16i32 and the table form of the fragments live in ss_device.h: ss_nearest.hip shares them.)
+// Fragments come from a 256-entry LDS table (4 codes of a byte -> the 4 one-hot VGPRs of a k-step
+// half, one ds_read_b128), not per-VGPR bit arithmetic (tools/tune_allpairs.hip measured the table
+// ahead).  The table, the tile choice and the sweep of a column block are ss_hamming.h's:
+// ss_nearest.hip runs the same tiles.
 // ------------------------------------------------------------------------------------------------
-template <int KS>
-__device__ __forceinline__ void onehot_frag(uint64_t word, bool valid, uint32_t P, uint32_t h, v4i32* f) {
-#pragma unroll
-    for (int s = 0; s < KS; ++s) {
-        v4i32 v;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const uint32_t p = 8u * s + 4u * h + q;
-            const uint32_t code = (uint32_t)(word >> (2u * p)) & 3u;
-            v[q] = (valid && p < P) ? (int)(1u << (8u * code)) : 0;
-        }
-        f[s] = v;
-    }
-}
-
 // Hit path of one 32 x 32 result tile (st = its 16 result registers per lane, [reg][lane], hit =
 // result >= 128: bit 7 or 8): index checks, LDS row / column counts, wave-aggregated pair append.
 __device__ __noinline__ void ap_hits(const AllPairsArgs& a, const int* st, uint32_t rl0, uint32_t cl, uint64_t row0,
@@ -218,15 +198,12 @@ __device__ __forceinline__ void tri_pair(uint64_t k, uint64_t t, uint32_t& bi, u
     bj = (uint32_t)(i + (int64_t)(k - before(i)));
 }
 
-// TAB: fragments from a 256-entry LDS table (4 codes of a byte -> the 4 one-hot VGPRs of a k-step
-// half, one ds_read_b128) instead of per-VGPR bit arithmetic.  Positions P .. 8 KS - 1 are then
-// code 0 on both sides and add the constant 8 KS - P to every result, folded into the threshold.
 // TRI: the launch may be a 1-D grid over upper-triangle tile pairs (kept out of the RB >= 4
 // instantiations: its registers cost them a wave per SIMD)
-template <int KS, int RB, bool TAB, bool TRI>
+template <int KS, int RB, bool TRI>
 __global__ __launch_bounds__(256) void k_allpairs_mfma(AllPairsArgs a, uint32_t P) {
-    constexpr int S = 4 * RB * 32;
-    constexpr int NW = (KS + 3) / 4;                       // packed words per read (32 positions each)
+    using T = MfmaTiles<KS, RB>;
+    constexpr int S = T::S, NW = T::NW;
     // one block per upper-triangle tile pair (a 1-D grid while its work-item count fits 32 bits;
     // beyond that the square 2-D grid, lower-triangle blocks exiting at once)
     uint32_t bi = blockIdx.y, bj = blockIdx.x;
@@ -235,13 +212,13 @@ __global__ __launch_bounds__(256) void k_allpairs_mfma(AllPairsArgs a, uint32_t 
     __shared__ uint64_t cw[S * NW];
     __shared__ uint32_t rowcnt[S], colcnt[S];
     __shared__ int stash[4 * 1024];                        // hit path: [wave][result reg][lane]
-    __shared__ v4i32 ohtab[TAB ? 256 : 1];
+    __shared__ v4i32 ohtab[256];
     __shared__ unsigned long long blkhits;
     const bool diag = bi == bj;
     if (threadIdx.x == 0) blkhits = 0;
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, h = lane >> 5, r = lane & 31u;
     const uint64_t row0 = (uint64_t)bi * S, col0 = (uint64_t)bj * S;
-    if (TAB) ohtab[threadIdx.x] = onehot_entry(threadIdx.x);
+    ohtab[threadIdx.x] = onehot_entry(threadIdx.x);
     for (int c = threadIdx.x; c < S; c += 256) {
         const uint64_t j = col0 + c;
 #pragma unroll
@@ -249,73 +226,19 @@ __global__ __launch_bounds__(256) void k_allpairs_mfma(AllPairsArgs a, uint32_t 
         rowcnt[c] = 0;
         colcnt[c] = 0;
     }
-    if (TAB) __syncthreads();
-    // k-step s covers positions 8s .. 8s+7 = byte 2(s % 4) + h of word s / 4 (4 codes per byte)
-    auto frag = [&](const uint64_t* word, bool valid, v4i32* f) {
-        if constexpr (TAB) {
-            onehot_frag_tab<KS>(ohtab, word, valid, h, f);
-        } else {
-            static_assert(TAB || NW == 1, "the arithmetic one-hot build is one-word only");
-            onehot_frag<KS>(word[0], valid, P, h, f);
-        }
-    };
+    __syncthreads();                                       // the table
     v4i32 A[RB][KS];
-#pragma unroll
-    for (int rb = 0; rb < RB; ++rb) {
-        const uint64_t i = row0 + (wave * RB + rb) * 32 + r;
-        uint64_t rw[NW];
-#pragma unroll
-        for (int w = 0; w < NW; ++w) rw[w] = (i < a.n && (uint32_t)w < a.W) ? a.words[i * a.wpr + w] : 0ull;
-        frag(rw, i < a.n, A[rb]);
-    }
+    T::load_a(ohtab, a.words, a.n, a.wpr, a.W, row0, A);
     __syncthreads();
-    // hit iff matches >= thr.  The accumulators start at 128 - thr, so a hit is a result >= 128.
-    // thr lies in [0, 8 KS] and matches in [0, 8 KS], 8 KS <= 128, so results lie in [0, 256] (256:
-    // identical 128-position rows at max distance >= 128): result >= 128 is bit 7 or bit 8, and an
-    // OR-reduction of the 16 non-negative registers has one of the two set exactly when one of them is
-    // >= 128, so one ballot tests a tile.  Max distance >= P: thr = 0 over the P positions, every pair hits.
-    const int thr = max(0, (int)P - (int)a.k) + (TAB ? 8 * KS - (int)P : 0);
-    v16i32 Cinit;
-#pragma unroll
-    for (int q = 0; q < 16; ++q) Cinit[q] = 128 - thr;
+    const v16i32 Cinit = T::c_init(T::thr(P, a.k));
     const uint32_t ncb = (uint32_t)min<uint64_t>(S / 32, (a.n - col0 + 31) / 32);
     for (uint32_t cb = 0; cb < ncb; ++cb) {
         const uint32_t cl = cb * 32 + r;                 // this lane's column (local)
         v4i32 B[KS];
-        frag(&cw[cl * NW], TAB ? true : col0 + cl < a.n, B);   // TAB: a padding column is "A..A" (filtered)
-        // RB >= 4 (short reads): all RB tiles of the column block first, one ballot for all of
-        // them: no branch between the tiles' MFMA chains, so they interleave; a hit (rare)
-        // recomputes the tiles below.  (100k x 12 nt: 14.7 -> 15.6 T pairs/s; at RB <= 2 the
-        // per-tile form measured faster.  Two tiles' chains explicitly interleaved with independent
-        // accumulators measured level at RB 8, slower at RB 4: profiles/r2/r2f/tune_ap_pair.log.)
-        if constexpr (RB >= 4) {
-            int any_all = 0;
-#pragma unroll
-            for (int rb = 0; rb < RB; ++rb) {
-                v16i32 D = __builtin_amdgcn_mfma_i32_32x32x32_i8(A[rb][0], B[0], Cinit, 0, 0, 0);
-#pragma unroll
-                for (int s2 = 1; s2 < KS; ++s2) D = __builtin_amdgcn_mfma_i32_32x32x32_i8(A[rb][s2], B[s2], D, 0, 0, 0);
-#pragma unroll
-                for (int q = 0; q < 16; ++q) any_all |= D[q];
-            }
-            if (!__ballot(any_all & 0x180)) continue;
-        }
-#pragma unroll
-        for (int rb = 0; rb < RB; ++rb) {
-            v16i32 D = __builtin_amdgcn_mfma_i32_32x32x32_i8(A[rb][0], B[0], Cinit, 0, 0, 0);
-#pragma unroll
-            for (int s2 = 1; s2 < KS; ++s2) D = __builtin_amdgcn_mfma_i32_32x32x32_i8(A[rb][s2], B[s2], D, 0, 0, 0);
-            int any = D[0];
-#pragma unroll
-            for (int q = 1; q < 16; ++q) any |= D[q];
-            if (!__ballot(any & 0x180)) continue;
-            // hit path (rare): the 16 results go through a per-wave LDS stash into an out-of-line
-            // loop, so the common path keeps its registers
-            int* st = stash + wave * 1024;
-#pragma unroll
-            for (int q = 0; q < 16; ++q) st[q * 64 + lane] = D[q];
+        onehot_frag_tab<KS>(ohtab, &cw[cl * NW], true, h, B);   // a padding column is "A..A" (filtered)
+        T::sweep(A, B, Cinit, stash, [&](int rb, const int* st) {
             ap_hits(a, st, (wave * RB + rb) * 32, cl, row0, col0, diag, rowcnt, colcnt, &blkhits);
-        }
+        });
     }
     __syncthreads();
     if (threadIdx.x == 0 && blkhits) atomicAdd(a.npairs, blkhits);
@@ -327,11 +250,9 @@ __global__ __launch_bounds__(256) void k_allpairs_mfma(AllPairsArgs a, uint32_t 
     }
 }
 
-// row blocks per wave: more A reuse for short reads, fewer registers for long ones
-// (tools/tune_allpairs.hip: KS 2 -> RB 8, KS 4 -> RB 2)
-template <int KS, int RB = (KS <= 2 ? 8 : (KS == 3 ? 4 : (KS == 4 ? 2 : 1))), bool TAB = true>
+template <int KS, int RB = mfma_rb(KS)>
 int launch_allpairs_mfma(AllPairsArgs a, uint32_t P, hipStream_t s) {
-    constexpr int S = 4 * RB * 32;
+    constexpr int S = MfmaTiles<KS, RB>::S;
     const uint64_t t = (a.n + S - 1) / S;
     if (t > 65535) return ss_fail(SS_EARG, "all-pairs: n too large for one launch (split the batch)");
     const uint64_t tri = t * (t + 1) / 2;
@@ -339,17 +260,16 @@ int launch_allpairs_mfma(AllPairsArgs a, uint32_t P, hipStream_t s) {
     // 1.80 -> 1.92), slower at RB 8 (100k x 12 nt 15.6 -> 13.3), where the square grid stays
     constexpr bool TRI = RB <= 2;
     const dim3 grid = (TRI && t > 1 && tri * 256 < (1ull << 32)) ? dim3((unsigned)tri) : dim3((unsigned)t, (unsigned)t);
-    hipLaunchKernelGGL((k_allpairs_mfma<KS, RB, TAB, TRI>), grid, dim3(256), 0, s, a, P);
+    hipLaunchKernelGGL((k_allpairs_mfma<KS, RB, TRI>), grid, dim3(256), 0, s, a, P);
     return ss_check(hipGetLastError(), "k_allpairs_mfma");
 }
 
-template <int WT, int R>
+template <int WT>
 int launch_allpairs(AllPairsArgs a, hipStream_t s) {
-    constexpr int S = Tile<WT, R>::S;
+    constexpr int S = Tile<WT>::S;
     const uint64_t t = (a.n + S - 1) / S;
     if (t > 65535) return ss_fail(SS_EARG, "all-pairs: n too large for one launch (split the batch)");
-    a.ntiles = (uint32_t)t;
-    hipLaunchKernelGGL((k_allpairs<WT, R>), dim3((unsigned)t, (unsigned)t), dim3(256), 0, s, a);
+    hipLaunchKernelGGL((k_allpairs<WT>), dim3((unsigned)t, (unsigned)t), dim3(256), 0, s, a);
     return ss_check(hipGetLastError(), "k_allpairs");
 }
 
@@ -369,30 +289,42 @@ int launch_allpairs(AllPairsArgs a, hipStream_t s) {
 // Buckets: the segment value itself when it has <= nbmax bits, else a 64-bit multiplicative hash of
 // it (colliding values only add candidates: the equality test is on the segment value).
 // ------------------------------------------------------------------------------------------------
-constexpr int kPigMaxG = 16;
+constexpr int kPigMaxG = 16;             // segments of the forms with row copies (k_pig_*, k_pigw_*)
+constexpr int kPiglMaxG = 32;            // the long form's segment bound (k_pigl_*, below)
 constexpr uint32_t kPigTile = 4096;      // buckets per scan tile: 256 threads x 16
 constexpr uint32_t kPigMaxBits = 22;     // <= 1024 tiles per segment (4 per thread of the scanning block)
 constexpr uint64_t kPigRatio = 16;       // auto: pigeonhole when candidates < all pairs / kPigRatio
 
+// One argument struct for the three forms: one-word rows (k_pig_*), W = 2 .. 4 with row copies
+// (k_pigw_*), and the long form without them (k_pigl_*, further below).  The one-word form's shift /
+// mask and the other forms' seg share their bytes (no kernel reads both): side by side the struct is
+// 608 B of kernel arguments, and past ~520 B the compiler builds k_pig_pairs' walks, unchanged in
+// source, with more exec-mask branches (100k x 16 nt, k 2: 0.099 -> 0.114 ms; profiles/hamming_refactor).
 struct PigArgs {
     const uint64_t* words;
     uint64_t n;
-    uint32_t wpr, k, G, nbmax, maxtiles, exact;   // exact: bit g = segment g buckets by value
-    uint32_t shift[kPigMaxG], nb[kPigMaxG];
-    uint64_t mask[kPigMaxG];
-    // multi-word reads (W = 2 .. 4, L 33 .. 128; k_pigw_*): segment g = positions [seg[g], seg[g + 1])
-    // of the row's 32 W positions (it may cross a word boundary)
-    uint32_t W;
-    uint32_t seg[kPigMaxG + 1];
+    uint32_t wpr, W, k, G, nbmax, maxtiles, exact, P;   // exact: bit g = segment g buckets by value
+    uint32_t nb[kPiglMaxG];
+    union {
+        struct {   // one-word rows (G <= kPigMaxG): segment g = (word >> shift[g]) & mask[g]
+            uint32_t shift[kPigMaxG];
+            uint64_t mask[kPigMaxG];
+        };
+        // multi-word rows: segment g = positions [seg[g], seg[g + 1]) of the row's P (it may cross a
+        // word boundary)
+        uint32_t seg[kPiglMaxG + 1];
+    };
     uint32_t* hist;       // G << nbmax: counts, then bucket starts (k_pig_apply)
     uint32_t* tile_cnt;   // G * maxtiles: bucket sums, then tile bases
     uint64_t* tile_cand;  // G * maxtiles
     uint64_t* cand;       // G: candidate pairs per segment
     uint32_t* done;       // k_pig_tile's finished-block count (zeroed with hist)
     uint32_t zero_out;    // k_pig_hist zeroes counts and *npairs (the entry point left them)
-    uint64_t* sw;         // G * n words in bucket order
+    uint64_t* sw;         // G * n * W words: the rows in bucket order (null in the long form)
     uint32_t* sid;        // G * n read indices in bucket order
-    uint32_t* rank;       // G * n: read i's rank in its bucket of segment g (k_pig_hist's atomics)
+    // G * n: read i's rank in its bucket of segment g (the hist kernels' atomics); the long form's
+    // scatter then overwrites it with that bucket's end
+    uint32_t* rank;
     uint32_t* counts;
     uint32_t* pairs;
     uint64_t max_pairs;
@@ -435,8 +367,7 @@ __device__ __forceinline__ T block_sum256(T v, T* red) {
 // per tile of 4096 buckets: number of reads and candidate pairs; the grid's last block to finish
 // then scans every segment's tile sums (<= 1024 tiles: 4 per thread) into tile bases and the
 // segment's candidate total -- no separate scan launch
-template <typename A>   // PigArgs or PiglArgs: only the histogram fields are read
-__global__ __launch_bounds__(256) void k_pig_tile(A a) {
+__global__ __launch_bounds__(256) void k_pig_tile(PigArgs a) {
     const uint32_t g = blockIdx.y, t0 = blockIdx.x * kPigTile, nbk = 1u << a.nb[g];
     __shared__ uint32_t r32[4];
     __shared__ uint64_t r64[4];
@@ -500,8 +431,7 @@ __global__ __launch_bounds__(256) void k_pig_tile(A a) {
 }
 
 // bucket starts: each thread owns 16 consecutive buckets of the tile
-template <typename A>
-__global__ __launch_bounds__(256) void k_pig_apply(A a) {
+__global__ __launch_bounds__(256) void k_pig_apply(PigArgs a) {
     const uint32_t g = blockIdx.y, t0 = blockIdx.x * kPigTile, nbk = 1u << a.nb[g];
     if (t0 >= nbk) return;
     uint32_t* h = a.hist + ((uint64_t)g << a.nbmax) + t0;
@@ -543,8 +473,6 @@ __global__ __launch_bounds__(256) void k_pig_scatter(PigArgs a) {
     }
 }
 
-// (WaveHits / hits_add / hits_flush, the per-wave LDS pair buffer, live in ss_device.h: ss_grouped.hip
-// shares them)
 constexpr uint64_t kPigTileWalk = 256;     // a wave's entry run past this: walked as broadcast tiles
 
 // one lane per read in bucket order of segment g = blockIdx.y, compared with the reads after it in its
@@ -667,26 +595,43 @@ __device__ __forceinline__ void pig_row(const PigArgs& a, uint64_t i, uint64_t (
 #pragma unroll
     for (int q = 0; q < W; ++q) w[q] = a.words[i * a.wpr + q];
 }
-// bits [2 b0, 2 b0 + 64) of a row (b0 in positions, < 32 W)
+// A row's words for the bucket function: in registers (W a template constant: selected, never
+// indexed) or in memory (a runtime W; no word at or past W is read).  word(q) = 0 for q >= W.
 template <int W>
-__device__ __forceinline__ uint64_t row_bits64(const uint64_t (&w)[W], uint32_t b0) {
-    const uint32_t q = b0 >> 5, sh = 2u * (b0 & 31u);
-    uint64_t lo = 0, hi = 0;
+struct RegRow {
+    const uint64_t (&w)[W];
+    __device__ __forceinline__ uint64_t word(uint32_t q) const {
+        uint64_t v = 0;
 #pragma unroll
-    for (int k = 0; k < W; ++k) {
-        if ((uint32_t)k == q) lo = w[k];
-        if ((uint32_t)k == q + 1u) hi = w[k];
+        for (int k = 0; k < W; ++k)
+            if ((uint32_t)k == q) v = w[k];
+        return v;
     }
-    return sh ? (lo >> sh) | (hi << (64u - sh)) : lo;
+};
+struct MemRow {
+    const uint64_t* r;
+    uint32_t W;
+    __device__ __forceinline__ uint64_t word(uint32_t q) const { return q < W ? r[q] : 0ull; }
+};
+// bits [2 b0, 2 b0 + 64) of a row (b0 in positions, < 32 W)
+template <typename Row>
+__device__ __forceinline__ uint64_t row_bits64(const Row& row, uint32_t b0) {
+    const uint32_t q = b0 >> 5, sh = 2u * (b0 & 31u);
+    const uint64_t lo = row.word(q);
+    if (!sh) return lo;
+    return (lo >> sh) | (row.word(q + 1u) << (64u - sh));
 }
-template <int W>
-__device__ __forceinline__ uint32_t pigw_bucket(const PigArgs& a, uint32_t g, const uint64_t (&w)[W]) {
+// bucket of segment g of a multi-word row: its value when it has <= nbmax bits, else a hash of it;
+// an empty segment is bucket 0
+template <typename Row>
+__device__ __forceinline__ uint32_t pigw_bucket(const PigArgs& a, uint32_t g, const Row& row) {
     const uint32_t p0 = a.seg[g], len = a.seg[g + 1] - p0;
-    if ((a.exact >> g) & 1u) return (uint32_t)(row_bits64<W>(w, p0) & ((1ull << (2u * len)) - 1ull));
+    if (!len) return 0u;
+    if ((a.exact >> g) & 1u) return (uint32_t)(row_bits64(row, p0) & ((1ull << (2u * len)) - 1ull));
     uint64_t h = 0x243F6A8885A308D3ull ^ len;
     for (uint32_t b = 0; b < len; b += 32) {          // the segment's 64-bit pieces, the last masked
         const uint32_t m = len - b < 32u ? len - b : 32u;
-        uint64_t v = row_bits64<W>(w, p0 + b);
+        uint64_t v = row_bits64(row, p0 + b);
         if (m < 32u) v &= (1ull << (2u * m)) - 1ull;
         h = (h ^ v) * 0x9E3779B97F4A7C15ull;
         h ^= h >> 29;
@@ -702,7 +647,7 @@ __global__ __launch_bounds__(256) void k_pigw_hist(PigArgs a) {
         uint64_t w[W];
         pig_row<W>(a, i, w);
         for (uint32_t g = 0; g < a.G; ++g)
-            a.rank[g * a.n + i] = atomicAdd(&a.hist[((uint64_t)g << a.nbmax) + pigw_bucket<W>(a, g, w)], 1u);
+            a.rank[g * a.n + i] = atomicAdd(&a.hist[((uint64_t)g << a.nbmax) + pigw_bucket(a, g, RegRow<W>{w})], 1u);
     }
 }
 
@@ -712,7 +657,7 @@ __global__ __launch_bounds__(256) void k_pigw_scatter(PigArgs a) {
         uint64_t w[W];
         pig_row<W>(a, i, w);
         for (uint32_t g = 0; g < a.G; ++g) {
-            const uint64_t pos = a.hist[((uint64_t)g << a.nbmax) + pigw_bucket<W>(a, g, w)] + a.rank[g * a.n + i];
+            const uint64_t pos = a.hist[((uint64_t)g << a.nbmax) + pigw_bucket(a, g, RegRow<W>{w})] + a.rank[g * a.n + i];
             uint64_t* dst = a.sw + ((uint64_t)g * a.n + pos) * W;
 #pragma unroll
             for (int q = 0; q < W; ++q) dst[q] = w[q];
@@ -742,7 +687,7 @@ __global__ __launch_bounds__(256) void k_pigw_pairs(PigArgs a) {
 #pragma unroll
     for (int q = 0; q < W; ++q) w[q] = valid ? sw[p * W + q] : 0ull;
     const uint32_t id = valid ? sid[p] : 0u;
-    const uint32_t b = pigw_bucket<W>(a, g, w);
+    const uint32_t b = pigw_bucket(a, g, RegRow<W>{w});
     const uint64_t end = valid ? (b + 1 < nbk ? start[b + 1] : a.n) : 0ull;
     constexpr uint64_t kLo = 0x5555555555555555ull;
     const uint32_t kmax = (uint32_t)__builtin_amdgcn_readfirstlane((int)a.k);
@@ -821,7 +766,6 @@ struct PigScratch {
     uint64_t* h_cand = nullptr;   // pinned: the candidate totals read back
 };
 PigScratch g_pig[64];
-constexpr int kPiglMaxG = 32;             // the long form's segment bound (k_pigl_*, below)
 
 // A call's hold on the scratch of the device that holds `words` (the kernels run there, on the
 // caller's stream), not of whichever device is current: that device made current and the
@@ -882,99 +826,8 @@ struct PigHold {
     }
 };
 
-// returns 0 with *done = false when the auto choice hands the batch to the tiled form
-int pig_all_pairs(const AllPairsArgs& b, uint32_t L, uint32_t P, bool forced, hipStream_t s, bool* done) {
-    *done = false;
-    PigArgs a{};
-    a.words = b.words;
-    a.n = b.n;
-    a.wpr = b.wpr;
-    a.k = b.k;
-    a.G = b.k + 1;
-    a.counts = b.counts;
-    a.pairs = b.pairs;
-    a.max_pairs = b.max_pairs;
-    a.npairs = b.npairs;
-    a.zero_out = 1;
-    a.W = b.W;
-    uint32_t lg = 0;
-    while ((1ull << lg) < a.n) ++lg;
-    a.nbmax = lg < 10 ? 10 : (lg > kPigMaxBits ? kPigMaxBits : lg);
-    a.maxtiles = ((1u << a.nbmax) + kPigTile - 1) / kPigTile;
-    // the L read positions split evenly (the first L % G segments one longer); the alias position L
-    // (P = L + 1: nearly always code 0, so no bucketing entropy) joins the last segment
-    const uint32_t Lr = P < L ? P : L;
-    for (uint32_t g = 0, pos = 0; g < a.G; ++g) {
-        uint32_t len = Lr / a.G + (g < Lr % a.G ? 1u : 0u);
-        if (g + 1 == a.G) len = P - pos;
-        a.shift[g] = 2 * pos;
-        a.mask[g] = len >= 32 ? ~0ull : ((1ull << (2 * len)) - 1ull);
-        a.nb[g] = 2 * len < a.nbmax ? 2 * len : a.nbmax;
-        if (2 * len <= a.nbmax) a.exact |= 1u << g;
-        a.seg[g] = pos;
-        pos += len;
-    }
-    a.seg[a.G] = P;
-    const size_t hist_n = (size_t)a.G << a.nbmax, tiles_n = (size_t)a.G * a.maxtiles;
-    const size_t need = tiles_n * 8 + a.G * 8 + (hist_n + 2) * 4 + tiles_n * 4 + 64 + (size_t)a.G * a.n * (8 * a.W + 8);
-    PigHold hold;
-    bool have = false;
-    int rc = hold.acquire(b.words, need, forced, s, a.npairs, a.counts, a.n, &have);
-    if (rc || !have) return rc;
-    PigScratch& ps = *hold.ps;
-    char* q = (char*)ps.p;
-    a.tile_cand = (uint64_t*)q;
-    a.cand = a.tile_cand + tiles_n;
-    a.sw = a.cand + a.G;
-    a.hist = (uint32_t*)(a.sw + (size_t)a.G * a.n * a.W);
-    a.done = a.hist + hist_n;                 // zeroed with hist
-    a.tile_cnt = a.done + 2;
-    a.sid = a.tile_cnt + tiles_n;
-    a.rank = a.sid + (size_t)a.G * a.n;
-    const unsigned rgrid = (unsigned)std::min<uint64_t>((a.n + 255) / 256, 2048);
-    const dim3 tgrid(a.maxtiles, a.G);
-    rc = ss_check(hipMemsetAsync(a.hist, 0, (hist_n + 2) * 4, s), "pig hist reset");
-    if (!rc) {
-        if (a.W == 1) hipLaunchKernelGGL(k_pig_hist, dim3(rgrid), dim3(256), 0, s, a);
-        else if (a.W == 2) hipLaunchKernelGGL(k_pigw_hist<2>, dim3(rgrid), dim3(256), 0, s, a);
-        else if (a.W == 3) hipLaunchKernelGGL(k_pigw_hist<3>, dim3(rgrid), dim3(256), 0, s, a);
-        else hipLaunchKernelGGL(k_pigw_hist<4>, dim3(rgrid), dim3(256), 0, s, a);
-        hipLaunchKernelGGL(k_pig_tile<PigArgs>, tgrid, dim3(256), 0, s, a);
-        rc = ss_check(hipGetLastError(), "k_pig_hist/tile");
-    }
-    bool use = forced;
-    if (!rc && !forced) {
-        rc = ss_check(hipMemcpyAsync(ps.h_cand, a.cand, a.G * 8, hipMemcpyDeviceToHost, s), "pig totals");
-        if (!rc) rc = ss_check(hipStreamSynchronize(s), "pig totals sync");
-        uint64_t cand = 0;
-        for (uint32_t g = 0; !rc && g < a.G; ++g) cand += ps.h_cand[g];
-        // measured (tools/probe_f4.py, profiles/r5/probe_f4_*.log): see kPigRatio
-        use = cand < a.n * (a.n - 1) / 2 / kPigRatio;
-    }
-    if (!rc && use) {
-        hipLaunchKernelGGL(k_pig_apply<PigArgs>, tgrid, dim3(256), 0, s, a);
-        if (a.W == 1) hipLaunchKernelGGL(k_pig_scatter, dim3(rgrid), dim3(256), 0, s, a);
-        else if (a.W == 2) hipLaunchKernelGGL(k_pigw_scatter<2>, dim3(rgrid), dim3(256), 0, s, a);
-        else if (a.W == 3) hipLaunchKernelGGL(k_pigw_scatter<3>, dim3(rgrid), dim3(256), 0, s, a);
-        else hipLaunchKernelGGL(k_pigw_scatter<4>, dim3(rgrid), dim3(256), 0, s, a);
-        const uint64_t pb = (a.n + 255) / 256;
-        if (pb > 0x7FFFFFFFull) rc = ss_fail(SS_EARG, "all-pairs: n too large");
-        else if (a.W == 2) hipLaunchKernelGGL(k_pigw_pairs<2>, dim3((unsigned)pb, a.G), dim3(256), 0, s, a);
-        else if (a.W == 3) hipLaunchKernelGGL(k_pigw_pairs<3>, dim3((unsigned)pb, a.G), dim3(256), 0, s, a);
-        else if (a.W == 4) hipLaunchKernelGGL(k_pigw_pairs<4>, dim3((unsigned)pb, a.G), dim3(256), 0, s, a);
-        else if (a.G <= 2) hipLaunchKernelGGL(k_pig_pairs<2>, dim3((unsigned)pb, a.G), dim3(256), 0, s, a);
-        else if (a.G <= 4) hipLaunchKernelGGL(k_pig_pairs<4>, dim3((unsigned)pb, a.G), dim3(256), 0, s, a);
-        else if (a.G <= 8) hipLaunchKernelGGL(k_pig_pairs<8>, dim3((unsigned)pb, a.G), dim3(256), 0, s, a);
-        else hipLaunchKernelGGL(k_pig_pairs<kPigMaxG>, dim3((unsigned)pb, a.G), dim3(256), 0, s, a);
-        if (!rc) rc = ss_check(hipGetLastError(), "k_pig_apply/scatter/pairs");
-        if (!rc) *done = true;
-    }
-    const int r2 = ss_check(hipEventRecord(ps.done, s), "pig scratch event");
-    return rc ? rc : r2;
-}
-
 // ------------------------------------------------------------------------------------------------
-// Long form (SS_ALLPAIRS_BUCKETED past pig_all_pairs' range: W = 5 .. 32 words, or max_dist 16 .. 31
+// Long form (SS_ALLPAIRS_BUCKETED past the range of the forms above: W = 5 .. 32 words, or max_dist 16 .. 31
 // at any W).  The same pigeonhole argument and segment split, for a runtime W and G <= 32.  Two
 // things differ from k_pigw_*:
 //  - no row copies: bucket order holds read indices only (sid), and candidate rows are read from
@@ -995,68 +848,24 @@ int pig_all_pairs(const AllPairsArgs& b, uint32_t L, uint32_t P, bool forced, hi
 // (112 VGPRs, 4 waves per SIMD): sparse buckets 0.124 -> 0.103 ms (100k x 150 nt, pool 2^16) and
 // 0.454 -> 0.358 ms (50k x 1024 nt), but buckets of ~400 reads 1.73 -> 2.16 ms and 2.52 -> 3.09 ms.
 // ------------------------------------------------------------------------------------------------
-struct PiglArgs {
-    const uint64_t* words;
-    uint64_t n;
-    uint32_t wpr, W, k, G, nbmax, maxtiles, exact, P;   // exact: bit g = segment g buckets by value
-    uint32_t nb[kPiglMaxG];
-    uint32_t seg[kPiglMaxG + 1];   // segment g = positions [seg[g], seg[g + 1]) of the row's P
-    uint32_t* hist;
-    uint32_t* tile_cnt;
-    uint64_t* tile_cand;
-    uint64_t* cand;
-    uint32_t* done;
-    uint32_t zero_out;
-    uint32_t* sid;        // G * n read indices in bucket order
-    uint32_t* rank;       // G * n: read i's rank in its bucket (k_pigl_hist), then that bucket's end (k_pigl_scatter)
-    uint32_t* counts;
-    uint32_t* pairs;
-    uint64_t max_pairs;
-    unsigned long long* npairs;
-};
-
-// bits [2 b0, 2 b0 + 64) of the row at r (b0 in positions, < 32 W); no word at or past W is read
-__device__ __forceinline__ uint64_t rowl_bits64(const uint64_t* r, uint32_t W, uint32_t b0) {
-    const uint32_t q = b0 >> 5, sh = 2u * (b0 & 31u);
-    const uint64_t lo = r[q];
-    if (!sh) return lo;
-    const uint64_t hi = q + 1u < W ? r[q + 1u] : 0ull;
-    return (lo >> sh) | (hi << (64u - sh));
-}
-// pigw_bucket for a runtime W (the same value and hash); an empty segment is bucket 0
-__device__ __forceinline__ uint32_t pigl_bucket(const PiglArgs& a, uint32_t g, const uint64_t* r) {
-    const uint32_t p0 = a.seg[g], len = a.seg[g + 1] - p0;
-    if (!len) return 0u;
-    if ((a.exact >> g) & 1u) return (uint32_t)(rowl_bits64(r, a.W, p0) & ((1ull << (2u * len)) - 1ull));
-    uint64_t h = 0x243F6A8885A308D3ull ^ len;
-    for (uint32_t b = 0; b < len; b += 32) {
-        const uint32_t m = len - b < 32u ? len - b : 32u;
-        uint64_t v = rowl_bits64(r, a.W, p0 + b);
-        if (m < 32u) v &= (1ull << (2u * m)) - 1ull;
-        h = (h ^ v) * 0x9E3779B97F4A7C15ull;
-        h ^= h >> 29;
-    }
-    return (uint32_t)(h >> (64 - a.nb[g]));
-}
-
 // a thread per read, every segment in turn (a thread per (segment, read) measured no faster at 100k x
 // 150 nt, 20 vs 20 us, and slower at 50k x 1024 nt, G = 17: hist 38 -> 43 us, scatter 27 -> 35 us)
-__global__ __launch_bounds__(256) void k_pigl_hist(PiglArgs a) {
+__global__ __launch_bounds__(256) void k_pigl_hist(PigArgs a) {
     if (a.zero_out && blockIdx.x == 0 && threadIdx.x == 0) *a.npairs = 0ull;
     for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < a.n; i += (uint64_t)gridDim.x * 256) {
         if (a.zero_out && a.counts) a.counts[i] = 0u;
         const uint64_t* r = a.words + i * a.wpr;
         for (uint32_t g = 0; g < a.G; ++g)
-            a.rank[g * a.n + i] = atomicAdd(&a.hist[((uint64_t)g << a.nbmax) + pigl_bucket(a, g, r)], 1u);
+            a.rank[g * a.n + i] = atomicAdd(&a.hist[((uint64_t)g << a.nbmax) + pigw_bucket(a, g, MemRow{r, a.W})], 1u);
     }
 }
 
-__global__ __launch_bounds__(256) void k_pigl_scatter(PiglArgs a) {
+__global__ __launch_bounds__(256) void k_pigl_scatter(PigArgs a) {
     for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < a.n; i += (uint64_t)gridDim.x * 256) {
         const uint64_t* r = a.words + i * a.wpr;
         for (uint32_t g = 0; g < a.G; ++g) {
             const uint32_t* start = a.hist + ((uint64_t)g << a.nbmax);
-            const uint32_t b = pigl_bucket(a, g, r), nbk = 1u << a.nb[g];
+            const uint32_t b = pigw_bucket(a, g, MemRow{r, a.W}), nbk = 1u << a.nb[g];
             const uint32_t pos = start[b] + a.rank[g * a.n + i];
             a.sid[g * a.n + pos] = (uint32_t)i;
             a.rank[g * a.n + i] = b + 1u < nbk ? start[b + 1u] : (uint32_t)a.n;   // this read's bucket end
@@ -1066,7 +875,7 @@ __global__ __launch_bounds__(256) void k_pigl_scatter(PiglArgs a) {
 
 constexpr int kPiglStep = 4;
 template <int LG>   // lanes per entry, one row word each: W <= LG
-__global__ __launch_bounds__(256) void k_pigl_pairs(PiglArgs a) {
+__global__ __launch_bounds__(256) void k_pigl_pairs(PigArgs a) {
     __shared__ uint2 pbuf[4][kPairBuf];
     __shared__ uint32_t s_seg[kPiglMaxG + 1];
     __shared__ unsigned long long s_hits;
@@ -1151,10 +960,20 @@ __global__ __launch_bounds__(256) void k_pigl_pairs(PiglArgs a) {
 // form ~1.5x ahead at the threshold, for batches whose rows no longer sit in L2 as these did.
 constexpr uint64_t kPiglRatio = 32;
 
+// The three forms of one chain (memset -> hist -> k_pig_tile -> [totals read back] -> k_pig_apply ->
+// scatter -> pairs): they differ in the kernels at those three points, in the per-row scratch and in
+// AUTO's ratio.
+enum PigForm { kPigWord, kPigRows, kPigLong };   // one-word rows; W = 2 .. 4 with row copies; long, without
+
+template <typename K>
+void pig_launch_w(K k2, K k3, K k4, uint32_t W, dim3 grid, hipStream_t s, const PigArgs& a) {
+    hipLaunchKernelGGL(W == 2 ? k2 : (W == 3 ? k3 : k4), grid, dim3(256), 0, s, a);
+}
+
 // returns 0 with *done = false when the auto choice hands the batch to the tiled form
-int pigl_all_pairs(const AllPairsArgs& b, uint32_t L, uint32_t P, bool forced, hipStream_t s, bool* done) {
+int pig_all_pairs(const AllPairsArgs& b, PigForm form, uint32_t L, uint32_t P, bool forced, hipStream_t s, bool* done) {
     *done = false;
-    PiglArgs a{};
+    PigArgs a{};
     a.words = b.words;
     a.n = b.n;
     a.wpr = b.wpr;
@@ -1171,20 +990,28 @@ int pigl_all_pairs(const AllPairsArgs& b, uint32_t L, uint32_t P, bool forced, h
     while ((1ull << lg) < a.n) ++lg;
     a.nbmax = lg < 10 ? 10 : (lg > kPigMaxBits ? kPigMaxBits : lg);
     a.maxtiles = ((1u << a.nbmax) + kPigTile - 1) / kPigTile;
-    // pig_all_pairs' split: the L read positions evenly (the first L % G segments one longer, a
-    // segment may be empty when L < G), the alias position L (P = L + 1) in the last
+    // the L read positions split evenly (the first L % G segments one longer, a segment may be empty
+    // when L < G); the alias position L (P = L + 1: nearly always code 0, so no bucketing entropy)
+    // joins the last segment
     const uint32_t Lr = P < L ? P : L;
     for (uint32_t g = 0, pos = 0; g < a.G; ++g) {
         uint32_t len = Lr / a.G + (g < Lr % a.G ? 1u : 0u);
         if (g + 1 == a.G) len = P - pos;
+        if (form == kPigWord) {
+            a.shift[g] = 2 * pos;
+            a.mask[g] = len >= 32 ? ~0ull : ((1ull << (2 * len)) - 1ull);
+        } else {
+            a.seg[g] = pos;
+        }
         a.nb[g] = 2 * len < a.nbmax ? 2 * len : a.nbmax;
         if (2 * len <= a.nbmax) a.exact |= 1u << g;
-        a.seg[g] = pos;
         pos += len;
     }
-    a.seg[a.G] = P;
+    if (form != kPigWord) a.seg[a.G] = P;
+    // per (segment, read): sid + rank, and the row's W words in the forms that keep a copy
+    const size_t ids_n = (size_t)a.G * a.n, sw_n = form == kPigLong ? 0 : ids_n * a.W;
     const size_t hist_n = (size_t)a.G << a.nbmax, tiles_n = (size_t)a.G * a.maxtiles;
-    const size_t need = tiles_n * 8 + a.G * 8 + (hist_n + 2) * 4 + tiles_n * 4 + 64 + (size_t)a.G * a.n * 8;
+    const size_t need = tiles_n * 8 + a.G * 8 + (hist_n + 2) * 4 + tiles_n * 4 + 64 + sw_n * 8 + ids_n * 8;
     PigHold hold;
     bool have = false;
     int rc = hold.acquire(b.words, need, forced, s, a.npairs, a.counts, a.n, &have);
@@ -1192,39 +1019,58 @@ int pigl_all_pairs(const AllPairsArgs& b, uint32_t L, uint32_t P, bool forced, h
     PigScratch& ps = *hold.ps;
     a.tile_cand = (uint64_t*)ps.p;
     a.cand = a.tile_cand + tiles_n;
-    a.hist = (uint32_t*)(a.cand + a.G);
+    a.sw = sw_n ? a.cand + a.G : nullptr;
+    a.hist = (uint32_t*)(a.cand + a.G + sw_n);
     a.done = a.hist + hist_n;                 // zeroed with hist
     a.tile_cnt = a.done + 2;
     a.sid = a.tile_cnt + tiles_n;
-    a.rank = a.sid + (size_t)a.G * a.n;
-    const unsigned rgrid = (unsigned)std::min<uint64_t>((a.n + 255) / 256, 2048);
+    a.rank = a.sid + ids_n;
+    const dim3 rgrid((unsigned)std::min<uint64_t>((a.n + 255) / 256, 2048));
     const dim3 tgrid(a.maxtiles, a.G);
-    rc = ss_check(hipMemsetAsync(a.hist, 0, (hist_n + 2) * 4, s), "pigl hist reset");
+    rc = ss_check(hipMemsetAsync(a.hist, 0, (hist_n + 2) * 4, s), "pig hist reset");
     if (!rc) {
-        hipLaunchKernelGGL(k_pigl_hist, dim3(rgrid), dim3(256), 0, s, a);
-        hipLaunchKernelGGL(k_pig_tile<PiglArgs>, tgrid, dim3(256), 0, s, a);
-        rc = ss_check(hipGetLastError(), "k_pigl_hist/tile");
+        if (form == kPigWord) hipLaunchKernelGGL(k_pig_hist, rgrid, dim3(256), 0, s, a);
+        else if (form == kPigRows) pig_launch_w(k_pigw_hist<2>, k_pigw_hist<3>, k_pigw_hist<4>, a.W, rgrid, s, a);
+        else hipLaunchKernelGGL(k_pigl_hist, rgrid, dim3(256), 0, s, a);
+        hipLaunchKernelGGL(k_pig_tile, tgrid, dim3(256), 0, s, a);
+        rc = ss_check(hipGetLastError(), "pigeonhole hist / k_pig_tile");
     }
     bool use = forced;
     if (!rc && !forced) {
-        rc = ss_check(hipMemcpyAsync(ps.h_cand, a.cand, a.G * 8, hipMemcpyDeviceToHost, s), "pigl totals");
-        if (!rc) rc = ss_check(hipStreamSynchronize(s), "pigl totals sync");
+        rc = ss_check(hipMemcpyAsync(ps.h_cand, a.cand, a.G * 8, hipMemcpyDeviceToHost, s), "pig totals");
+        if (!rc) rc = ss_check(hipStreamSynchronize(s), "pig totals sync");
         uint64_t cand = 0;
         for (uint32_t g = 0; !rc && g < a.G; ++g) cand += ps.h_cand[g];
-        use = cand < a.n * (a.n - 1) / 2 / kPiglRatio;
+        // measured (tools/probe_f4.py, profiles/r5/probe_f4_*.log, profiles/r7/probe_f4_longsweep.log):
+        // see kPigRatio, kPiglRatio
+        use = cand < a.n * (a.n - 1) / 2 / (form == kPigLong ? kPiglRatio : kPigRatio);
     }
     if (!rc && use) {
-        hipLaunchKernelGGL(k_pig_apply<PiglArgs>, tgrid, dim3(256), 0, s, a);
-        hipLaunchKernelGGL(k_pigl_scatter, dim3(rgrid), dim3(256), 0, s, a);
-        const int lgn = a.W <= 4 ? 4 : (a.W <= 8 ? 8 : (a.W <= 16 ? 16 : 32));
+        hipLaunchKernelGGL(k_pig_apply, tgrid, dim3(256), 0, s, a);
+        if (form == kPigWord) hipLaunchKernelGGL(k_pig_scatter, rgrid, dim3(256), 0, s, a);
+        else if (form == kPigRows) pig_launch_w(k_pigw_scatter<2>, k_pigw_scatter<3>, k_pigw_scatter<4>, a.W, rgrid, s, a);
+        else hipLaunchKernelGGL(k_pigl_scatter, rgrid, dim3(256), 0, s, a);
+        // entries per block of the pairs kernel: a lane each, or in the long form a group of lgn lanes
+        // (the power of two >= W, at least 4)
+        const int lgn = form != kPigLong ? 1 : (a.W <= 4 ? 4 : (a.W <= 8 ? 8 : (a.W <= 16 ? 16 : 32)));
         const uint64_t pb = (a.n + 256 / lgn - 1) / (256 / lgn);
         const dim3 pgrid((unsigned)pb, a.G);
-        if (pb > 0x7FFFFFFFull) rc = ss_fail(SS_EARG, "all-pairs: n too large");
-        else if (lgn == 4) hipLaunchKernelGGL(k_pigl_pairs<4>, pgrid, dim3(256), 0, s, a);
-        else if (lgn == 8) hipLaunchKernelGGL(k_pigl_pairs<8>, pgrid, dim3(256), 0, s, a);
-        else if (lgn == 16) hipLaunchKernelGGL(k_pigl_pairs<16>, pgrid, dim3(256), 0, s, a);
-        else hipLaunchKernelGGL(k_pigl_pairs<32>, pgrid, dim3(256), 0, s, a);
-        if (!rc) rc = ss_check(hipGetLastError(), "k_pig_apply / k_pigl_scatter / k_pigl_pairs");
+        if (pb > 0x7FFFFFFFull) {
+            rc = ss_fail(SS_EARG, "all-pairs: n too large");
+        } else if (form == kPigWord) {
+            if (a.G <= 2) hipLaunchKernelGGL(k_pig_pairs<2>, pgrid, dim3(256), 0, s, a);
+            else if (a.G <= 4) hipLaunchKernelGGL(k_pig_pairs<4>, pgrid, dim3(256), 0, s, a);
+            else if (a.G <= 8) hipLaunchKernelGGL(k_pig_pairs<8>, pgrid, dim3(256), 0, s, a);
+            else hipLaunchKernelGGL(k_pig_pairs<kPigMaxG>, pgrid, dim3(256), 0, s, a);
+        } else if (form == kPigRows) {
+            pig_launch_w(k_pigw_pairs<2>, k_pigw_pairs<3>, k_pigw_pairs<4>, a.W, pgrid, s, a);
+        } else {
+            if (lgn == 4) hipLaunchKernelGGL(k_pigl_pairs<4>, pgrid, dim3(256), 0, s, a);
+            else if (lgn == 8) hipLaunchKernelGGL(k_pigl_pairs<8>, pgrid, dim3(256), 0, s, a);
+            else if (lgn == 16) hipLaunchKernelGGL(k_pigl_pairs<16>, pgrid, dim3(256), 0, s, a);
+            else hipLaunchKernelGGL(k_pigl_pairs<32>, pgrid, dim3(256), 0, s, a);
+        }
+        if (!rc) rc = ss_check(hipGetLastError(), "k_pig_apply / pigeonhole scatter / pairs");
         if (!rc) *done = true;
     }
     const int r2 = ss_check(hipEventRecord(ps.done, s), "pig scratch event");
@@ -1249,13 +1095,13 @@ int ss_hamming_all_pairs_ex(const uint64_t* d_words, uint64_t n, uint32_t L, uin
     if (method == SS_ALLPAIRS_BUCKETED && max_dist >= (uint32_t)kPiglMaxG)
         return ss_fail(SS_EARG, "bucketed all-pairs needs max_dist <= 31");
     if (L > SS_MAX_NT) return ss_fail(SS_EARG, "L must be <= 1024");
-    const uint32_t W = L <= 32u ? 1u : (L + 31u) / 32u;
+    const uint32_t W = ham_shape(L).W;
     if (wpr < W || wpr > 32) return ss_fail(SS_EARG, "bad wpr");
     if (!d_npairs) return ss_fail(SS_EARG, "d_npairs is required");
     if (n >= (1ull << 32)) return ss_fail(SS_EARG, "n must be < 2^32");
     hipStream_t s = (hipStream_t)stream;
     // the pigeonhole form (tried first when it may apply) zeroes the outputs in its first kernel
-    const uint32_t Pw = L + 1 < 32u * W ? L + 1 : 32u * W;
+    const uint32_t Pw = ham_shape(L).P;
     // the methods' ranges are the caller's max_dist (forced methods refuse by it); the work below runs
     // on max_dist clamped to Pw (no distance exceeds the Pw compared positions, so the results are
     // the same), which keeps Gw = max_dist + 1 in [1, Pw + 1]: max_dist = 2^32 - 1 would wrap it to 0
@@ -1295,7 +1141,6 @@ int ss_hamming_all_pairs_ex(const uint64_t* d_words, uint64_t n, uint32_t L, uin
     a.wpr = wpr;
     a.W = W;
     a.k = max_dist;
-    a.ntiles = 0;
     a.counts = d_counts;
     a.pairs = d_pairs;
     a.max_pairs = d_pairs ? max_pairs : 0;
@@ -1305,32 +1150,21 @@ int ss_hamming_all_pairs_ex(const uint64_t* d_words, uint64_t n, uint32_t L, uin
     // auto: segments of >= 3 nt and a batch large enough to pay the host read of the totals
     if (pig_try) {
         bool done = false;
-        rc = pig_all_pairs(a, L, Pw, pig_forced, s, &done);
+        rc = pig_all_pairs(a, W == 1 ? kPigWord : kPigRows, L, Pw, pig_forced, s, &done);
         if (rc || done) return rc;
     }
     if (pigl_try) {
         bool done = false;
-        rc = pigl_all_pairs(a, L, Pw, method == SS_ALLPAIRS_BUCKETED, s, &done);
+        rc = pig_all_pairs(a, kPigLong, L, Pw, method == SS_ALLPAIRS_BUCKETED, s, &done);
         if (rc || done) return rc;
     }
     if (W <= 4) {
-        // MFMA form: P = min(L + 1, 32 W) positions (the alias bit of the tail block can sit at
-        // position L), 8 per k-step; k-steps rounded up to an instantiated count (the padding
-        // positions are code 0 on both sides and shift every result by the same constant)
-        const uint32_t P = L + 1 < 32u * W ? L + 1 : 32u * W;
-        const uint32_t ks = (P + 7) / 8;
-        if (ks <= 1) return launch_allpairs_mfma<1>(a, P, s);
-        if (ks <= 2) return launch_allpairs_mfma<2>(a, P, s);
-        if (ks <= 3) return launch_allpairs_mfma<3>(a, P, s);
-        if (ks <= 4) return launch_allpairs_mfma<4>(a, P, s);
-        if (ks <= 6) return launch_allpairs_mfma<6>(a, P, s);
-        if (ks <= 8) return launch_allpairs_mfma<8>(a, P, s);
-        if (ks <= 12) return launch_allpairs_mfma<12>(a, P, s);
-        return launch_allpairs_mfma<16>(a, P, s);
+        // MFMA form: the Pw compared positions, 8 per k-step, k-steps rounded up to an instantiated count
+        return with_mfma_ks(mfma_ks(Pw), [&](auto ks) { return launch_allpairs_mfma<decltype(ks)::value>(a, Pw, s); });
     }
-    if (W <= 8) return launch_allpairs<8, 1>(a, s);
-    if (W <= 16) return launch_allpairs<16, 1>(a, s);
-    return launch_allpairs<32, 1>(a, s);
+    if (W <= 8) return launch_allpairs<8>(a, s);
+    if (W <= 16) return launch_allpairs<16>(a, s);
+    return launch_allpairs<32>(a, s);
 }
 
 }  // extern "C"

@@ -1,7 +1,8 @@
 // ss_device.h — gfx950 device primitives shared by the encode / decode / hamming / counter kernels.
 //
 // The codec pieces are integer SWAR on 32-bit lanes (4 ASCII bytes per VGPR): no MFMA, no LDS tables.
-// The hamming tiles' shared pieces (bit planes, one-hot MFMA fragments from an LDS table) follow them.
+// The counter's hashes and the first-invalid-read reports follow them.  What only the hamming pair
+// kernels share (bit planes, pair buffers, the MFMA tiles) is in ss_hamming.h.
 // Bit contract (README.md:101-112): code(c) = (c >> 1) & 3 for A C T G (0 1 2 3);
 // nt j of a read lives in word j/32 at bits 2*(j%32).
 #pragma once
@@ -96,104 +97,6 @@ __device__ __forceinline__ void st_stream(uint4* p, uint4 v) {
 __device__ __forceinline__ uint32_t ham32(uint32_t x) { return __popc(((x >> 1) | x) & 0x55555555u); }
 __device__ __forceinline__ uint32_t ham64(uint64_t x) {
     return __popcll(((x >> 1) | x) & 0x5555555555555555ull);
-}
-
-// even bits of x (nt codes' low bits) -> 32-bit plane; odd bits -> the other plane
-// (the bit-plane hamming tiles of ss_allpairs.hip / ss_nearest.hip)
-__device__ __forceinline__ uint32_t even_bits(uint64_t x) {
-    x &= 0x5555555555555555ull;
-    x = (x | (x >> 1)) & 0x3333333333333333ull;
-    x = (x | (x >> 2)) & 0x0F0F0F0F0F0F0F0Full;
-    x = (x | (x >> 4)) & 0x00FF00FF00FF00FFull;
-    x = (x | (x >> 8)) & 0x0000FFFF0000FFFFull;
-    x = (x | (x >> 16)) & 0x00000000FFFFFFFFull;
-    return (uint32_t)x;
-}
-
-// {lo, hi} planes of the W compared words of row r of a packed batch (stride wpr); a row past n and the
-// words W .. WT-1 of the template are zero (k_allpairs, k_gp_pairs)
-template <int WT>
-__device__ __forceinline__ void load_planes(const uint64_t* words, uint64_t n, uint32_t wpr, uint32_t W, uint64_t r,
-                                            uint32_t* lo, uint32_t* hi) {
-#pragma unroll
-    for (int w = 0; w < WT; ++w) {
-        uint64_t x = 0;
-        if (r < n && (uint32_t)w < W) x = words[r * wpr + w];
-        lo[w] = even_bits(x);
-        hi[w] = even_bits(x >> 1);
-    }
-}
-
-// Hit output of a wave without one global atomic per hit ballot (the pigeonhole pair kernels of
-// ss_allpairs.hip, k_gp_pairs): pairs gather in a per-wave LDS buffer and leave in runs (one
-// pair-counter atomic per run of up to kPairBuf); count-only calls keep the wave's hit count in a
-// register and add it once.  A: any argument struct with pairs, max_pairs and npairs.
-constexpr uint32_t kPairBuf = 512;
-struct WaveHits {
-    uint2* buf;          // this wave's kPairBuf LDS entries
-    uint32_t fill = 0;   // wave-uniform
-    uint64_t nh = 0;     // wave-uniform (count-only)
-};
-__device__ __forceinline__ void lds_wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-template <typename A>
-__device__ __forceinline__ void hits_flush(const A& a, WaveHits& wh) {
-    if (!wh.fill) return;
-    lds_wave_sync();
-    const uint32_t lane = threadIdx.x & 63u;
-    unsigned long long base = 0;
-    if (lane == 0) base = atomicAdd(a.npairs, (unsigned long long)wh.fill);
-    base = __shfl(base, 0);
-    for (uint32_t e = lane; e < wh.fill; e += 64) {
-        const uint64_t slot = base + e;
-        if (slot < a.max_pairs) {
-            const uint2 pr = wh.buf[e];
-            a.pairs[2 * slot] = pr.x;
-            a.pairs[2 * slot + 1] = pr.y;
-        }
-    }
-    lds_wave_sync();
-    wh.fill = 0;
-}
-template <typename A>
-__device__ __forceinline__ void hits_add(const A& a, WaveHits& wh, bool hit, uint64_t mask, uint32_t i, uint32_t j) {
-    const uint32_t c = (uint32_t)__popcll(mask);
-    if (!a.pairs) {
-        wh.nh += c;
-        return;
-    }
-    if (wh.fill + c > kPairBuf) hits_flush(a, wh);
-    const uint32_t lane = threadIdx.x & 63u;
-    if (hit) wh.buf[wh.fill + __popcll(mask & ((1ull << lane) - 1ull))] = make_uint2(min(i, j), max(i, j));
-    wh.fill += c;
-}
-
-// One-hot i8 fragments of v_mfma_i32_32x32x32_i8 for the hamming tiles (ss_allpairs.hip's header
-// has the scheme): position p of a read -> 4 int8 lanes with a 1 at its code.  A 256-entry LDS
-// table maps the 4 codes of a byte to the 4 one-hot VGPRs of a k-step half (one ds_read_b128):
-// thread t of a 256-thread block writes tab[t] = onehot_entry(t).  k-step s covers positions
-// 8s .. 8s+7 = byte 2(s % 4) + h of word s / 4 (h = lane >> 5).
-typedef int v4i32 __attribute__((ext_vector_type(4)));
-typedef int v16i32 __attribute__((ext_vector_type(16)));
-
-__device__ __forceinline__ v4i32 onehot_entry(uint32_t byte) {
-    v4i32 e;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) e[q] = (int)(1u << (8u * ((byte >> (2 * q)) & 3u)));
-    return e;
-}
-
-template <int KS>
-__device__ __forceinline__ void onehot_frag_tab(const v4i32* tab, const uint64_t* word, bool valid, uint32_t h, v4i32* f) {
-#pragma unroll
-    for (int s2 = 0; s2 < KS; ++s2) {
-        const v4i32 z = {0, 0, 0, 0};
-        const uint32_t byte = (uint32_t)(word[s2 / 4] >> (16 * (s2 % 4) + 8 * h)) & 0xFFu;
-        f[s2] = valid ? tab[byte] : z;
-    }
 }
 
 __host__ __device__ __forceinline__ uint64_t splitmix64(uint64_t x) {

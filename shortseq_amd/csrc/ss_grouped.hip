@@ -18,15 +18,16 @@
 // walks in all: the VALU all-pairs tiles' work, no MFMA -- ss_hamming_all_pairs is the tool for one group
 // of 10^5 rows ("Grouped all-pairs").  Hits leave the loop through a wave ballot: row
 // counts stay in registers, column counts go to LDS, pairs gather in the waves' LDS buffers
-// (WaveHits, ss_device.h) and are appended with one global atomic per block.
+// (WaveHits, ss_hamming.h) and are appended with one global atomic per block.
 //
 // Malformed offsets are not detected on the device, but nothing depends on them for memory safety:
 // the search reads off[1 .. ngroups] only, every end is clamped to n, end <= i means "no partners",
 // and a written index is a row index i < n or a column j < end <= n.
 #include <algorithm>
 
-#include "ss_device.h"
+#include "ss_hamming.h"
 #include "ss_internal.h"
+#include "host_codec.h"   // after the public header (it declares ss_err only without it)
 
 namespace {
 
@@ -176,20 +177,10 @@ __global__ __launch_bounds__(256) void k_gp_pairs(GpArgs a) {
 
 const char* gp_check(uint64_t n, uint64_t ngroups, uint32_t L, uint32_t wpr) {
     if (L < 1 || L > SS_MAX_NT) return "grouped all-pairs: L must be 1 .. 1024";
-    const uint32_t W = L <= 32u ? 1u : (L + 31u) / 32u;
-    if (wpr < W) return "grouped all-pairs: wpr below the words of L";
+    if (wpr < ham_shape(L).W) return "grouped all-pairs: wpr below the words of L";
     if (n >= (1ull << 32)) return "grouped all-pairs: n must be < 2^32";
     if (n && !ngroups) return "grouped all-pairs: rows without a group";
     return nullptr;
-}
-
-inline uint32_t host_ham_words(const uint64_t* x, const uint64_t* y, uint32_t W) {
-    uint32_t d = 0;
-    for (uint32_t w = 0; w < W; ++w) {
-        const uint64_t v = x[w] ^ y[w];
-        d += (uint32_t)__builtin_popcountll(((v >> 1) | v) & 0x5555555555555555ull);
-    }
-    return d;
 }
 
 }  // namespace
@@ -217,7 +208,7 @@ int ss_hamming_all_pairs_grouped_ex(const uint64_t* d_words, uint64_t n, uint32_
     a.n = n;
     a.ngroups = ngroups;
     a.wpr = wpr;
-    a.W = L <= 32u ? 1u : (L + 31u) / 32u;
+    a.W = ham_shape(L).W;
     a.k = max_dist;
     a.counts = d_counts;
     a.pairs = max_pairs ? d_pairs : nullptr;
@@ -262,14 +253,13 @@ int ss_host_hamming_all_pairs_grouped(const uint64_t* h_words, uint64_t n, uint3
     if (h_npairs) *h_npairs = 0;
     if (h_counts) std::fill(h_counts, h_counts + n, 0u);
     if (n < 2) return SS_OK;
-    const uint32_t W = L <= 32u ? 1u : (L + 31u) / 32u;
     if (!max_pairs) h_pairs = nullptr;
     uint64_t total = 0;
     for (uint64_t g = 0; g < ngroups; ++g) {
         const uint64_t beg = h_group_offsets[g], end = h_group_offsets[g + 1];
         for (uint64_t i = beg; i + 1 < end; ++i) {
             for (uint64_t j = i + 1; j < end; ++j) {
-                if (host_ham_words(h_words + i * wpr, h_words + j * wpr, W) > max_dist) continue;
+                if (ssh::hamming(h_words + i * wpr, h_words + j * wpr, L) > max_dist) continue;
                 if (h_counts) {
                     ++h_counts[i];
                     ++h_counts[j];

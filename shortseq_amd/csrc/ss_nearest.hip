@@ -26,7 +26,7 @@
 // registers, its running best in registers), reference planes staged in LDS.  Correct, not tuned.
 #include <algorithm>
 
-#include "ss_device.h"
+#include "ss_hamming.h"
 #include "ss_internal.h"
 #include "host_codec.h"   // after the public header (it declares ss_err only without it)
 
@@ -106,8 +106,8 @@ __device__ __forceinline__ void near_store(const NearArgs& a, uint64_t i, uint32
 
 template <int KS, int RB>
 __global__ __launch_bounds__(256) void k_nearest_mfma(NearArgs a, uint32_t P) {
-    constexpr int S = 4 * RB * 32;
-    constexpr int NW = (KS + 3) / 4;                       // packed words per row (32 positions each)
+    using T = MfmaTiles<KS, RB>;
+    constexpr int S = T::S, NW = T::NW;
     __shared__ uint64_t cw[kStage * NW];
     __shared__ uint32_t rs_d[S], rs_i[S], rs_n[S];         // per query row: best distance, lowest index, count
     __shared__ int stash[4 * 1024];                        // hit path: [wave][result reg][lane]
@@ -124,21 +124,10 @@ __global__ __launch_bounds__(256) void k_nearest_mfma(NearArgs a, uint32_t P) {
     }
     v4i32 A[RB][KS];
     __syncthreads();                                       // the table
-#pragma unroll
-    for (int rb = 0; rb < RB; ++rb) {
-        const uint64_t i = row0 + (wave * RB + rb) * 32 + r;
-        uint64_t rw[NW];
-#pragma unroll
-        for (int w = 0; w < NW; ++w) rw[w] = (i < a.nq && (uint32_t)w < a.W) ? a.q[i * a.q_wpr + w] : 0ull;
-        onehot_frag_tab<KS>(ohtab, rw, i < a.nq, h, A[rb]);
-    }
-    // k_allpairs_mfma's threshold: hit iff matches >= thr over the 8 KS table positions (P compared
-    // + 8 KS - P padding positions, code 0 on both sides); results lie in [0, 256], a hit is >= 128
-    const int thr = max(0, (int)P - (int)a.k) + (8 * KS - (int)P);
+    T::load_a(ohtab, a.q, a.nq, a.q_wpr, a.W, row0, A);
+    const int thr = T::thr(P, a.k);
     const int bias = 8 * KS + 128 - thr;                   // distance of a result v = bias - v
-    v16i32 Cinit;
-#pragma unroll
-    for (int q = 0; q < 16; ++q) Cinit[q] = 128 - thr;
+    const v16i32 Cinit = T::c_init(thr);
     for (uint64_t s0 = c_beg; s0 < c_end; s0 += kStage) {
         __syncthreads();                                   // the previous stage is read
         for (int c = threadIdx.x; c < kStage; c += 256) {
@@ -153,36 +142,9 @@ __global__ __launch_bounds__(256) void k_nearest_mfma(NearArgs a, uint32_t P) {
             const bool cvalid = s0 + cl < c_end;           // a padding column is "A..A": filtered by index
             v4i32 B[KS];
             onehot_frag_tab<KS>(ohtab, &cw[cl * NW], true, h, B);
-            // RB >= 4: every tile of the column block first and one ballot for all of them, as
-            // k_allpairs_mfma does (no branch between the tiles' MFMA chains); a hit recomputes below
-            if constexpr (RB >= 4) {
-                int any_all = 0;
-#pragma unroll
-                for (int rb = 0; rb < RB; ++rb) {
-                    v16i32 D = __builtin_amdgcn_mfma_i32_32x32x32_i8(A[rb][0], B[0], Cinit, 0, 0, 0);
-#pragma unroll
-                    for (int s2 = 1; s2 < KS; ++s2) D = __builtin_amdgcn_mfma_i32_32x32x32_i8(A[rb][s2], B[s2], D, 0, 0, 0);
-#pragma unroll
-                    for (int q = 0; q < 16; ++q) any_all |= D[q];
-                }
-                if (!__ballot(any_all & 0x180)) continue;
-            }
-#pragma unroll
-            for (int rb = 0; rb < RB; ++rb) {
-                v16i32 D = __builtin_amdgcn_mfma_i32_32x32x32_i8(A[rb][0], B[0], Cinit, 0, 0, 0);
-#pragma unroll
-                for (int s2 = 1; s2 < KS; ++s2) D = __builtin_amdgcn_mfma_i32_32x32x32_i8(A[rb][s2], B[s2], D, 0, 0, 0);
-                int any = D[0];
-#pragma unroll
-                for (int q = 1; q < 16; ++q) any |= D[q];
-                if (!__ballot(any & 0x180)) continue;
-                // the 16 results go through a per-wave LDS stash into an out-of-line loop, so the
-                // sweep keeps its registers
-                int* st = stash + wave * 1024;
-#pragma unroll
-                for (int q = 0; q < 16; ++q) st[q * 64 + lane] = D[q];
+            T::sweep(A, B, Cinit, stash, [&](int rb, const int* st) {
                 near_hits(st, (wave * RB + rb) * 32, (uint32_t)(s0 + cb * 32), cvalid, bias, rs_d, rs_i, rs_n);
-            }
+            });
         }
     }
     __syncthreads();
@@ -256,19 +218,13 @@ struct NearPlan {
     uint64_t per_split;     // columns per range, a multiple of 32
 };
 
-// the instantiated k-step counts and their row blocks per wave (k_allpairs_mfma's choice)
-uint32_t near_ks(uint32_t P) {
-    const uint32_t ks = (P + 7) / 8;
-    return ks <= 4 ? ks : (ks <= 6 ? 6 : (ks <= 8 ? 8 : (ks <= 12 ? 12 : 16)));
-}
-uint32_t near_rb(uint32_t ks) { return ks <= 2 ? 8 : (ks == 3 ? 4 : (ks == 4 ? 2 : 1)); }
-
 NearPlan near_plan(uint64_t nq, uint64_t nr, uint32_t L, uint32_t ref_splits) {
     NearPlan p{};
-    p.W = L <= 32u ? 1u : (L + 31u) / 32u;
-    p.P = L + 1 < 32u * p.W ? L + 1 : 32u * p.W;
-    p.ks = p.W <= 4 ? near_ks(p.P) : 0;
-    p.S = p.ks ? 4 * near_rb(p.ks) * 32 : 256;
+    const HamShape sh = ham_shape(L);
+    p.W = sh.W;
+    p.P = sh.P;
+    p.ks = p.W <= 4 ? mfma_ks(p.P) : 0;
+    p.S = p.ks ? 4 * mfma_rb((int)p.ks) * 32 : 256;
     const uint64_t cblocks = (nr + 31) / 32;
     uint64_t want = ref_splits;
     if (!want) {
@@ -288,15 +244,10 @@ uint64_t near_ws(const NearPlan& p, uint64_t nq) { return p.splits > 1 ? 12ull *
 
 const char* near_check(uint64_t nq, uint32_t q_wpr, uint64_t nr, uint32_t r_wpr, uint32_t L) {
     if (L < 1 || L > SS_MAX_NT) return "nearest: L must be 1 .. 1024";
-    const uint32_t W = L <= 32u ? 1u : (L + 31u) / 32u;
+    const uint32_t W = ham_shape(L).W;
     if (q_wpr < W || r_wpr < W) return "nearest: q_wpr / r_wpr below the words of L";
     if (nq >= (1ull << 32) || nr >= (1ull << 32)) return "nearest: nq and nr must be < 2^32";
     return nullptr;
-}
-
-template <int KS>
-void launch_near_mfma(const NearArgs& a, uint32_t P, dim3 grid, hipStream_t s) {
-    hipLaunchKernelGGL((k_nearest_mfma<KS, (KS <= 2 ? 8 : (KS == 3 ? 4 : (KS == 4 ? 2 : 1)))>), grid, dim3(256), 0, s, a, P);
 }
 
 }  // namespace
@@ -348,19 +299,17 @@ int ss_hamming_nearest_ex(const uint64_t* d_q, uint64_t nq, uint32_t q_wpr, cons
     for (uint64_t t0 = 0; t0 < tiles; t0 += kMaxTilesPerLaunch) {
         a.tile0 = t0;
         const dim3 grid((unsigned)std::min<uint64_t>(kMaxTilesPerLaunch, tiles - t0), p.splits);
-        switch (p.ks) {
-            case 1: launch_near_mfma<1>(a, p.P, grid, s); break;
-            case 2: launch_near_mfma<2>(a, p.P, grid, s); break;
-            case 3: launch_near_mfma<3>(a, p.P, grid, s); break;
-            case 4: launch_near_mfma<4>(a, p.P, grid, s); break;
-            case 6: launch_near_mfma<6>(a, p.P, grid, s); break;
-            case 8: launch_near_mfma<8>(a, p.P, grid, s); break;
-            case 12: launch_near_mfma<12>(a, p.P, grid, s); break;
-            case 16: launch_near_mfma<16>(a, p.P, grid, s); break;
-            default:
-                if (p.W <= 8) hipLaunchKernelGGL(k_nearest_valu<8>, grid, dim3(256), 0, s, a);
-                else if (p.W <= 16) hipLaunchKernelGGL(k_nearest_valu<16>, grid, dim3(256), 0, s, a);
-                else hipLaunchKernelGGL(k_nearest_valu<32>, grid, dim3(256), 0, s, a);
+        if (p.ks) {
+            with_mfma_ks(p.ks, [&](auto ks) {
+                constexpr int KS = decltype(ks)::value;
+                hipLaunchKernelGGL((k_nearest_mfma<KS, mfma_rb(KS)>), grid, dim3(256), 0, s, a, p.P);
+            });
+        } else if (p.W <= 8) {
+            hipLaunchKernelGGL(k_nearest_valu<8>, grid, dim3(256), 0, s, a);
+        } else if (p.W <= 16) {
+            hipLaunchKernelGGL(k_nearest_valu<16>, grid, dim3(256), 0, s, a);
+        } else {
+            hipLaunchKernelGGL(k_nearest_valu<32>, grid, dim3(256), 0, s, a);
         }
         const int rc = ss_check(hipGetLastError(), "k_nearest tiles");
         if (rc) return rc;

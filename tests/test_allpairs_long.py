@@ -77,6 +77,7 @@ LONG_CASES = [
     (1024, 300, 31),   # W = 32, every lane's word live, G = 32
     (64, 900, 20),     # W <= 4, k >= 16: the long form on short rows
     (20, 1000, 16),    # W = 1, 17 segments of 1-2 nt
+    (20, 300, 21),     # G = 22 over P = 21 positions: an empty segment (bucket 0) reports every pair
     (96, 1000, 5),     # the delegated path (the existing pigeonhole form)
 ]
 
@@ -224,6 +225,75 @@ def test_auto_long_reads_is_capturable(gpu, oracle):
     g.replay()
     torch.cuda.synchronize(gpu)
     assert int(tot.item()) == tot_e and torch.equal(cnt, cnt_e)
+
+
+FORM_SEQUENCE = [
+    (12, 1, "pigeonhole"),     # one-word form
+    (150, 3, "bucketed"),      # long form, 8 lanes per entry
+    (40, 2, "pigeonhole"),     # W = 2 with row copies
+    (20, 20, "bucketed"),      # long form at W = 1, k >= 16: 21 one-position segments (20 nt + the alias position)
+    (12, 1, "pigeonhole"),     # the one-word form again
+]
+
+
+@functools.lru_cache(maxsize=None)
+def _form_case(L, n, k):
+    """n rows drawn from a pool of 40 random reads, each copied with 0 .. k + 1 substitutions at random
+    positions (fixed seed), and their brute-force counts / sorted pairs (int64 [m, 2]); shared, callers
+    do not modify them.  One-word rows (L <= 32, the table path) draw their substitutions from all eight
+    valid bytes: an aliased last byte (\x01 \x03 \x07 \x14) sets the bit at position L, which the
+    distance counts, so two 20-nt rows can be 21 apart and (L 20, k 20) does not hit every pair."""
+    import oracle
+    rng = np.random.default_rng(1000 * L + k)
+    pool = oracle.gen_reads(1000 * L + k, 0, 40, L).reshape(40, L)
+    rows = pool[rng.integers(0, 40, size=n)].copy()
+    alphabet = np.frombuffer(b"ACGT\x01\x03\x07\x14" if L <= 32 else b"ACGT", np.uint8)
+    nsub = rng.integers(0, k + 2, size=n)
+    for i in np.flatnonzero(nsub):
+        pos = rng.integers(0, L, size=nsub[i])
+        rows[i, pos] = alphabet[rng.integers(0, alphabet.size, size=nsub[i])]
+    words, rc, _ = oracle.encode_batch(rows.reshape(-1), n, L)
+    assert rc == 0
+    words = np.ascontiguousarray(words).reshape(n, -1)
+    words.setflags(write=False)
+    cnt = np.zeros(n, dtype=np.int64)
+    pairs = []
+    for i in range(n - 1):                       # _brute, with the pairs kept as arrays (up to 12.5 M of them)
+        d = oracle.hamming_ref_batch(words[i + 1:], n - i - 1, L, words[i])
+        js = np.flatnonzero(d <= k) + i + 1
+        cnt[i] += js.size
+        cnt[js] += 1
+        pairs.append(np.stack([np.full(js.size, i, dtype=np.int64), js.astype(np.int64)], axis=1))
+    return words, cnt, np.concatenate(pairs)
+
+
+@pytest.mark.gpu
+def test_forms_share_the_scratch_back_to_back(gpu, oracle):
+    """The three pigeonhole forms through one driver and one per-device grow-only scratch, back to back
+    in one process: the sequence at n = 300 (more than one 256-thread block, a partial last wave), then
+    at n = 5000 (the scratch freed and regrown between forms).  Every call: counts, total and sorted
+    pairs equal brute force (then count-only and a 3-pair truncation, as _check), on inputs whose
+    brute-force total is neither 0 nor every pair."""
+    import torch
+    import shortseq_amd.batch as B
+    for n in (300, 5000):
+        for L, k, method in FORM_SEQUENCE:
+            words, cnt_e, pairs_e = _form_case(L, n, k)
+            m = pairs_e.shape[0]
+            print(f"n {n} L {L} k {k} {method}: brute-force total {m} of {n * (n - 1) // 2}")
+            assert 0 < m < n * (n - 1) // 2
+            d = torch.from_numpy(words.view(np.int64).copy()).to(gpu)
+            cnt, pairs, total = B.hamming_all_pairs(d, L, k, max_pairs=m + 10, method=method)
+            assert total == m
+            assert np.array_equal(cnt.cpu().numpy().astype(np.int64), cnt_e)
+            assert np.array_equal(pairs.cpu().numpy().astype(np.int64), pairs_e)
+            cnt2, _, total2 = B.hamming_all_pairs(d, L, k, method=method)
+            assert total2 == total and torch.equal(cnt2, cnt)
+            _, p3, total3 = B.hamming_all_pairs(d, L, k, counts=False, max_pairs=3, method=method)
+            assert total3 == total and p3.shape[0] == 3
+            key = pairs_e[:, 0] * n + pairs_e[:, 1]             # sorted: the brute force runs in (i, j) order
+            k3 = p3.cpu().numpy().astype(np.int64)
+            assert bool(np.isin(k3[:, 0] * n + k3[:, 1], key).all())
 
 
 def test_method_table_and_header_constant():
