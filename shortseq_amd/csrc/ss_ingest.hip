@@ -38,8 +38,6 @@
 // skipped while rows <= capacity / 2); class tables grow through ss_counter_extract_words +
 // ss_counter_merge_words (a length rare in the first chunk and common later).
 #include <fcntl.h>
-#include <pthread.h>
-#include <sched.h>
 #include <sys/stat.h>
 #include <unistd.h>
 
@@ -50,13 +48,12 @@
 #include <cmath>
 #include <atomic>
 #include <chrono>
-#include <condition_variable>
 #include <map>
-#include <mutex>
 #include <string>
 #include <thread>
 #include <vector>
 
+#include "fq_reader.h"
 #include "ss_internal.h"
 
 namespace {
@@ -778,19 +775,102 @@ struct HBuf {
     }
 };
 
-// the FASTQ reader ring (ss_ingest_add_fastq_range): a slot is one chunk, pinned and on the device
-constexpr uint64_t kFqPiece = 64ull << 20;           // file read / H2D piece
+// The engine's side of the FASTQ reader ring (fq_reader.h; ss_ingest_add_fastq_range): the two slots'
+// buffers -- a slot is one chunk, pinned and on the device -- the copy stream and the stage split,
+// driven by the reader through FqSlotOps.
 constexpr uint64_t kFqChunkDefault = 1ull << 30;     // chunk bytes when the caller passes 0
-struct FqSlot {
-    HBuf h;
-    DBuf<uint8_t> d;
-    hipEvent_t done = nullptr;    // the slot's H2D pieces are complete (recorded on fq_copy)
-    std::vector<hipEvent_t> ev;   // 2 timing events per H2D piece
-    uint32_t np = 0;              // pieces of the chunk in the slot
-    uint64_t n = 0, use = 0;      // bytes in the slot, bytes up to its last newline (n at the range's end)
-    bool at_eof = false;
-    int rc = SS_OK;
-    std::string err;              // the reader's error message (its last-error string is thread-local)
+struct FqState final : FqSlotOps {
+    struct Slot {
+        HBuf h;
+        DBuf<uint8_t> d;
+        hipEvent_t done = nullptr;    // the slot's H2D pieces are complete (recorded on copy)
+        std::vector<hipEvent_t> ev;   // 2 timing events per H2D piece
+    } slot[2];
+    int device = 0;
+    hipStream_t copy = nullptr;       // the reader thread's H2D pieces
+    // the reader thread's CPUs: the GPU's NUMA node's (ss_gpu_numa_cpus; looked up once, node -2
+    // until then), so the pinned slots it allocates and the file bytes it copies in are node-local
+    std::vector<int> cpus;
+    int node = -2;
+    // FASTQ stage split since the last ss_ingest_fastq_stages (VERDICT r5 item 7): host ms of the file
+    // reads, device ms of the H2D pieces (event pairs, summed), host ms of the index (to its sync), of
+    // the chunk counts (process_chunk) and of ss_ingest_finish; the bytes the H2D pieces moved
+    double ms[5] = {};
+    uint64_t h2d_bytes = 0;
+    DBuf<uint64_t> ws, aux, counts;   // the device index's workspace (index_chunk)
+
+    // the copy stream, the slots' done events and the CPU list, each made once
+    int prepare(int dev) {
+        device = dev;
+        int rc = SS_OK;
+        if (!copy) rc = ss_check(hipStreamCreateWithFlags(&copy, hipStreamNonBlocking), "ingest fastq stream");
+        for (int i = 0; i < 2 && !rc; ++i)
+            if (!slot[i].done) rc = ss_check(hipEventCreateWithFlags(&slot[i].done, hipEventDisableTiming), "ingest fastq event");
+        if (node == -2) {
+            int allowed = 0;
+            cpus = ss_gpu_numa_cpus(device, &node, &allowed);
+            const char* env = getenv("SHORTSEQ_FQ_PIN");
+            if (env && env[0] == '0') cpus.clear();
+        }
+        return rc;
+    }
+    void release() {
+        for (Slot& sl : slot) {
+            for (hipEvent_t e : sl.ev) (void)hipEventDestroy(e);
+            sl.ev.clear();
+            if (sl.done) (void)hipEventDestroy(sl.done);
+            sl.done = nullptr;
+            sl.h.release(), sl.d.release();
+        }
+        if (copy) (void)hipStreamDestroy(copy);
+        copy = nullptr;
+        ws.release(), aux.release(), counts.release();
+    }
+    // the summed device ms of the first np H2D pieces of slot i (all complete)
+    double pieces_ms(int i, uint32_t np) const {
+        double sum = 0;
+        for (uint32_t q = 0; q < np; ++q) {
+            float t = 0;
+            if (hipEventElapsedTime(&t, slot[i].ev[2 * q], slot[i].ev[2 * q + 1]) == hipSuccess) sum += t;
+            else (void)hipGetLastError();
+        }
+        return sum;
+    }
+
+    void thread_start() override { (void)hipSetDevice(device); }
+    int ensure(int i, uint64_t cap, uint8_t** host) override {
+        int rc;
+        if ((rc = slot[i].h.ensure(cap)) || (rc = slot[i].d.ensure(cap + 16))) return rc;
+        *host = slot[i].h.p;
+        return SS_OK;
+    }
+    int queue_copy(int i, uint32_t piece, uint64_t off, uint64_t len) override {
+        Slot& sl = slot[i];
+        // (a piece number's first use only: the events stay with the slot)
+        while (sl.ev.size() < 2 * (piece + 1)) {
+            sl.ev.reserve(sl.ev.size() + 2);      // so that no event is lost to a failed push_back
+            hipEvent_t e = nullptr;
+            if (int rc = ss_check(hipEventCreate(&e), "ingest fastq event")) return rc;
+            sl.ev.push_back(e);
+        }
+        int rc = ss_check(hipEventRecord(sl.ev[2 * piece], copy), "ingest fastq event");
+        if (!rc) rc = ss_check(hipMemcpyAsync(sl.d.p + off, sl.h.p + off, len, hipMemcpyHostToDevice, copy), "ingest H2D");
+        if (!rc) rc = ss_check(hipEventRecord(sl.ev[2 * piece + 1], copy), "ingest fastq event");
+        h2d_bytes += len;
+        return rc;
+    }
+    int wait_copies() override { return ss_check(hipStreamSynchronize(copy), "ingest fastq grow"); }
+    int grow(int i, uint64_t cap, uint64_t keep, uint8_t** host) override {
+        HBuf grown;
+        if (int rc = grown.ensure(cap)) return rc;
+        memcpy(grown.p, slot[i].h.p, keep);
+        slot[i].h.release();
+        slot[i].h = grown;
+        *host = grown.p;
+        return SS_OK;
+    }
+    int complete(int i) override { return ss_check(hipEventRecord(slot[i].done, copy), "ingest fastq event"); }
+    const char* last_error() override { return ss_last_error_string(); }
 };
 
 struct Group {
@@ -851,7 +931,6 @@ struct ss_ingest {
                                    // sketch (tests: forces the SS_EFULL path) -- ss_ingest_set_exact
     DBuf<uint64_t> first_bad;      // [kLenBins + 1]: one u64 per length bin, the class encode's last
     uint64_t* h_bad = nullptr;     // pinned [3 kLenBins + 8]: first-bad and overflow words, a size query
-    DBuf<uint64_t> fq_ws, fq_aux, fq_counts;
     std::map<uint32_t, Group> groups;
     std::vector<std::pair<uint64_t, ss_counter*>> pool;    // idle tables (capacity, handle)
     uint64_t nreads = 0;           // global read index of the next read
@@ -900,17 +979,7 @@ struct ss_ingest {
     uint64_t nkeys = 0, nwords = 0;
     DBuf<uint64_t> slot, ordered, woff, scan;
     DBuf<GDesc> gdesc;
-    // FASTQ stage split since the last ss_ingest_fastq_stages (VERDICT r5 item 7): host ms of the file
-    // reads, device ms of the H2D pieces (event pairs, summed), host ms of the index (to its sync), of
-    // the chunk counts (process_chunk) and of ss_ingest_finish; the bytes the H2D pieces moved
-    double fq_ms[5] = {};
-    uint64_t fq_h2d_bytes = 0;
-    FqSlot fq[2];
-    hipStream_t fq_copy = nullptr;     // the reader thread's H2D pieces
-    // the reader thread's CPUs: the GPU's NUMA node's (ss_gpu_numa_cpus; looked up once, fq_node -2
-    // until then), so the pinned slots it allocates and the file bytes it copies in are node-local
-    std::vector<int> fq_cpus;
-    int fq_node = -2;
+    FqState fq;                    // the FASTQ reader ring's slots, copy stream, index workspace, stage split
 };
 
 namespace {
@@ -1857,35 +1926,42 @@ int extract_groups(ss_ingest* g, std::vector<Group*>& placed, bool flat = false)
     return SS_OK;
 }
 
-// ---- FASTQ file reading (parallel preads into the pinned staging buffer) ---------------------------
-uint64_t pread_full(int fd, uint8_t* dst, uint64_t len, uint64_t pos) {
-    uint64_t got = 0;
-    while (got < len) {
-        const ssize_t k = pread(fd, dst + got, len - got, (off_t)(pos + got));
-        if (k <= 0) break;
-        got += (uint64_t)k;
+// ---- FASTQ chunks ----------------------------------------------------------------------------------
+// The device index of a chunk's first `use` bytes (ss_fastq_index_onepass into offs / dlens), run again
+// with more room while the record capacity or the staging overflowed; *nl = its newlines, *nrec = its
+// records.  Synchronises the engine's stream.
+int index_chunk(ss_ingest* g, const uint8_t* d_buf, uint64_t use, uint64_t line0, bool at_eof, uint64_t* nl,
+                uint64_t* nrec) {
+    hipStream_t s = g->stream;
+    FqState& fq = g->fq;
+    for (uint64_t maxr = use / 16 + 2;;) {
+        const uint64_t wsb = ss_fastq_onepass_ws_bytes(use, maxr);
+        int rc;
+        if ((rc = fq.ws.ensure(wsb / 8 + 1)) || (rc = g->offs.ensure(maxr)) || (rc = g->dlens.ensure(maxr)) ||
+            (rc = fq.aux.ensure(maxr)) || (rc = fq.counts.ensure(3)))
+            return rc;
+        rc = ss_fastq_index_onepass(d_buf, use, line0, at_eof ? 1 : 0, fq.ws.p, wsb, g->offs.p, g->dlens.p, fq.aux.p,
+                                    maxr, fq.counts.p, s);
+        if (!rc) rc = ss_check(hipMemcpyAsync(g->h_bad, fq.counts.p, 24, hipMemcpyDeviceToHost, s), "ingest fq");
+        if (!rc) rc = ss_check(hipStreamSynchronize(s), "ingest fq");
+        if (rc) return rc;
+        *nl = g->h_bad[0];
+        *nrec = g->h_bad[1];
+        if (g->h_bad[2]) maxr *= 2;
+        else if (*nrec <= maxr) return SS_OK;
+        else maxr = *nrec;
     }
-    return got;
 }
 
-uint64_t read_parallel(int fd, uint8_t* dst, uint64_t len, uint64_t pos, unsigned threads) {
-    if (len < (32ull << 20) || threads <= 1) return pread_full(fd, dst, len, pos);
-    const uint64_t per = ((len + threads - 1) / threads + (1 << 20) - 1) & ~((uint64_t)(1 << 20) - 1);
-    std::vector<std::thread> ts;
-    std::vector<uint64_t> got(threads, 0);
-    for (unsigned t = 0; t < threads; ++t) {
-        const uint64_t a = (uint64_t)t * per;
-        if (a >= len) break;
-        const uint64_t b = std::min(len, a + per);
-        ts.emplace_back([&, t, a, b] { got[t] = pread_full(fd, dst + a, b - a, pos + a); });
+// the file descriptor of one call, closed however the call ends
+struct Fd {
+    const int v;
+    explicit Fd(int fd) : v(fd) {}
+    Fd(const Fd&) = delete;
+    ~Fd() {
+        if (v >= 0) close(v);
     }
-    uint64_t sum = 0;
-    for (size_t t = 0; t < ts.size(); ++t) {
-        ts[t].join();
-        sum += got[t];
-    }
-    return sum;
-}
+};
 
 }  // namespace
 
@@ -1990,20 +2066,11 @@ int ss_ingest_destroy(ss_ingest* g) {
     g->groups.clear();
     for (auto& p : g->pool) ss_counter_destroy(p.second);
     g->pool.clear();
-    for (FqSlot& sl : g->fq) {
-        for (hipEvent_t e : sl.ev) (void)hipEventDestroy(e);
-        sl.ev.clear();
-        if (sl.done) (void)hipEventDestroy(sl.done);
-        sl.done = nullptr;
-        sl.h.release(), sl.d.release();
-    }
-    if (g->fq_copy) (void)hipStreamDestroy(g->fq_copy);
-    g->fq_copy = nullptr;
+    g->fq.release();
     g->stage.release();
     g->out_host.release();
     g->dbuf.release(), g->offs.release(), g->dlens.release(), g->order.release(), g->blkhist.release();
     g->blkfirst.release(), g->split_out.release(), g->rows.release(), g->first_bad.release();
-    g->fq_ws.release(), g->fq_aux.release(), g->fq_counts.release();
     g->slot.release(), g->ordered.release(), g->woff.release(), g->scan.release(), g->gdesc.release();
     g->cls_words.release(), g->cls_fps.release(), g->hll.release(), g->ovf.release();
     g->cls_flag.release(), g->zero32.release();
@@ -2079,13 +2146,10 @@ int ss_ingest_add_fastq(ss_ingest* g, const char* path, uint64_t chunk_bytes, ui
 
 int ss_fastq_split(const char* path, uint32_t nparts, uint64_t* h_begin, uint64_t* h_line0) {
     if (!path || !nparts || !h_begin || !h_line0) return ss_fail(SS_EARG, "null argument");
-    const int fd = open(path, O_RDONLY);
-    if (fd < 0) return ss_fail(SS_EARG, "cannot open the FASTQ file");
+    const Fd fd(open(path, O_RDONLY));
+    if (fd.v < 0) return ss_fail(SS_EARG, "cannot open the FASTQ file");
     struct stat st;
-    if (fstat(fd, &st) != 0) {
-        close(fd);
-        return ss_fail(SS_EARG, "cannot stat the FASTQ file");
-    }
+    if (fstat(fd.v, &st) != 0) return ss_fail(SS_EARG, "cannot stat the FASTQ file");
     const uint64_t size = (uint64_t)st.st_size;
     // part p starts right after the first newline at or past p * size / nparts (part 0 at 0); parts
     // may come out empty (begin[p] == begin[p + 1]) when lines are long
@@ -2095,7 +2159,7 @@ int ss_fastq_split(const char* path, uint32_t nparts, uint64_t* h_begin, uint64_
     for (uint32_t p = 1; p < nparts; ++p) {
         uint64_t pos = std::max(b[p - 1], size * p / nparts), at = size;
         while (pos < size && at == size) {
-            const uint64_t got = pread_full(fd, buf.data(), std::min<uint64_t>(buf.size(), size - pos), pos);
+            const uint64_t got = pread_full(fd.v, buf.data(), std::min<uint64_t>(buf.size(), size - pos), pos);
             if (got == 0) break;
             const void* nl = memchr(buf.data(), '\n', got);
             if (nl) at = pos + (uint64_t)((const uint8_t*)nl - buf.data()) + 1;
@@ -2105,21 +2169,20 @@ int ss_fastq_split(const char* path, uint32_t nparts, uint64_t* h_begin, uint64_
     }
     // newlines before each part: the parts' newline counts (one thread per part), prefix-summed
     std::vector<uint64_t> nl(nparts, 0);
-    std::vector<std::thread> ts;
+    JoinedThreads th;
     for (uint32_t p = 0; p + 1 < nparts; ++p)
-        ts.emplace_back([&, p] {
+        th.ts.emplace_back([&, p] {
             std::vector<uint8_t> tb(1 << 20);
             uint64_t cnt = 0;
             for (uint64_t pos = b[p]; pos < b[p + 1];) {
-                const uint64_t got = pread_full(fd, tb.data(), std::min<uint64_t>(tb.size(), b[p + 1] - pos), pos);
+                const uint64_t got = pread_full(fd.v, tb.data(), std::min<uint64_t>(tb.size(), b[p + 1] - pos), pos);
                 if (got == 0) break;
                 for (uint64_t k = 0; k < got; ++k) cnt += tb[k] == '\n';
                 pos += got;
             }
             nl[p] = cnt;
         });
-    for (auto& t : ts) t.join();
-    close(fd);
+    th.join();
     uint64_t run = 0;
     for (uint32_t p = 0; p < nparts; ++p) {
         h_begin[p] = b[p];
@@ -2134,231 +2197,58 @@ int ss_ingest_add_fastq_range(ss_ingest* g, const char* path, uint64_t begin, ui
                               uint64_t chunk_bytes, uint64_t* h_nseqs) {
     if (!g || !path) return ss_fail(SS_EARG, "null argument");
     (void)hipSetDevice(g->device);
-    const int fd = open(path, O_RDONLY);
-    if (fd < 0) return ss_fail(SS_EARG, "cannot open the FASTQ file");
+    const Fd fd(open(path, O_RDONLY));
+    if (fd.v < 0) return ss_fail(SS_EARG, "cannot open the FASTQ file");
     struct stat st;
-    if (fstat(fd, &st) != 0) {
-        close(fd);
-        return ss_fail(SS_EARG, "cannot stat the FASTQ file");
-    }
+    if (fstat(fd.v, &st) != 0) return ss_fail(SS_EARG, "cannot stat the FASTQ file");
     // the range [begin, end) of the file: it starts at a line boundary and ends at the file's end or
     // right after a newline, so its last line is complete (the strlen - 1 rule of a final line with no
     // newline applies only at the file's end)
     const uint64_t size = std::min<uint64_t>((uint64_t)st.st_size, end);
     if (h_nseqs) *h_nseqs = 0;
-    if (begin >= size) {
-        close(fd);
-        return SS_OK;
-    }
+    if (begin >= size) return SS_OK;
     if (chunk_bytes == 0) chunk_bytes = kFqChunkDefault;
-    const uint64_t cap0 = std::max<uint64_t>(16, std::min<uint64_t>(chunk_bytes, size - begin + 16));
+    const uint64_t cap0 = fq_cap0(chunk_bytes, size - begin);
     hipStream_t s = g->stream;
-    int rc = SS_OK;
-    if (!g->fq_copy) rc = ss_check(hipStreamCreateWithFlags(&g->fq_copy, hipStreamNonBlocking), "ingest fastq stream");
-    for (int i = 0; i < 2 && !rc; ++i)
-        if (!g->fq[i].done) rc = ss_check(hipEventCreateWithFlags(&g->fq[i].done, hipEventDisableTiming), "ingest fastq event");
-    if (rc) {
-        close(fd);
-        return rc;
-    }
+    FqState& fq = g->fq;
+    int rc = fq.prepare(g->device);
+    if (rc) return rc;
     const uint64_t seqs0 = g->nreads;
     const unsigned threads = std::max(1u, std::min(8u, std::thread::hardware_concurrency()));
     using Clock = std::chrono::steady_clock;
     auto since = [](Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); };
-    // The reader ring: a reader thread fills chunk k + 1 into slot (k + 1) & 1 -- the previous chunk's
-    // tail (bytes after its last newline) first, then file reads in pieces of kFqPiece, each piece's
-    // H2D queued on fq_copy as soon as it is read -- while this thread indexes and counts chunk k
-    // from slot k & 1 on the engine's stream.  A slot goes back to the reader once the engine's
-    // stream has finished with it.  state[i]: 0 the reader's, 1 filled (this thread's).
-    std::mutex mu;
-    std::condition_variable cv;
-    int state[2] = {0, 0};
-    bool stop = false;
-    if (g->fq_node == -2) {
-        int allowed = 0;
-        g->fq_cpus = ss_gpu_numa_cpus(g->device, &g->fq_node, &allowed);
-        const char* env = getenv("SHORTSEQ_FQ_PIN");
-        if (env && env[0] == '0') g->fq_cpus.clear();
-    }
-    auto reader = [&]() {
-        (void)hipSetDevice(g->device);
-        if (!g->fq_cpus.empty()) {     // (read_parallel's threads inherit the mask)
-            cpu_set_t set;
-            CPU_ZERO(&set);
-            for (int c : g->fq_cpus) CPU_SET(c, &set);
-            (void)pthread_setaffinity_np(pthread_self(), sizeof(set), &set);
-        }
-        uint64_t pos = begin, cap = cap0, carry = 0;
-        const uint8_t* csrc = nullptr;
-        for (uint64_t k = 0;; ++k) {
-            FqSlot& sl = g->fq[k & 1];
-            {
-                std::unique_lock<std::mutex> lk(mu);
-                cv.wait(lk, [&] { return stop || state[k & 1] == 0; });
-                if (stop) return;
-            }
-            int r = SS_OK;
-            sl.np = 0;
-            try {
-                for (;;) {
-                    if (cap >= (1ull << 32)) {
-                        r = ss_fail(SS_EARG, "a FASTQ line is longer than 2 GiB");
-                        break;
-                    }
-                    if ((r = sl.h.ensure(cap)) || (r = sl.d.ensure(cap + 16))) break;
-                    if (carry && csrc != sl.h.p) memcpy(sl.h.p, csrc, carry);
-                    uint8_t* hv = sl.h.p;
-                    const uint64_t want = std::min(cap - carry, size - std::min(size, pos));
-                    const uint64_t npieces = (want + kFqPiece - 1) / kFqPiece + 1;
-                    while (sl.ev.size() < 2 * (sl.np + npieces) && !r) {
-                        hipEvent_t e = nullptr;
-                        r = ss_check(hipEventCreate(&e), "ingest fastq event");
-                        if (!r) sl.ev.push_back(e);
-                    }
-                    if (r) break;
-                    auto h2d = [&](uint64_t off, uint64_t len) {
-                        int q = ss_check(hipEventRecord(sl.ev[2 * sl.np], g->fq_copy), "ingest fastq event");
-                        if (!q) q = ss_check(hipMemcpyAsync(sl.d.p + off, hv + off, len, hipMemcpyHostToDevice, g->fq_copy), "ingest H2D");
-                        if (!q) q = ss_check(hipEventRecord(sl.ev[2 * sl.np + 1], g->fq_copy), "ingest fastq event");
-                        ++sl.np;
-                        g->fq_h2d_bytes += len;
-                        return q;
-                    };
-                    if (carry) r = h2d(0, carry);
-                    uint64_t got = 0;
-                    for (uint64_t off = 0; off < want && !r; off += kFqPiece) {
-                        const uint64_t len = std::min(kFqPiece, want - off);
-                        const auto t0 = Clock::now();
-                        const uint64_t n = read_parallel(fd, hv + carry + off, len, pos + off, threads);
-                        g->fq_ms[0] += since(t0);
-                        got += n;
-                        if (n != len) break;
-                        r = h2d(carry + off, len);
-                    }
-                    if (r) break;
-                    if (got != want) {
-                        r = ss_fail(SS_EHIP, "short read of the FASTQ file");
-                        break;
-                    }
-                    pos += got;
-                    sl.n = carry + got;
-                    sl.at_eof = pos >= size;
-                    sl.use = sl.n;
-                    if (sl.at_eof || sl.n == 0) break;
-                    sl.use = 0;
-                    for (uint64_t q = sl.n; q > 0; --q)
-                        if (hv[q - 1] == '\n') {
-                            sl.use = q;
-                            break;
-                        }
-                    if (sl.use) break;
-                    // one line fills the chunk: grow this slot (its bytes kept, sent again as the carry)
-                    if ((r = ss_check(hipStreamSynchronize(g->fq_copy), "ingest fastq grow"))) break;
-                    HBuf grown;
-                    if ((r = grown.ensure(2 * cap))) break;
-                    memcpy(grown.p, hv, sl.n);
-                    sl.h.release();
-                    sl.h = grown;
-                    cap *= 2;
-                    carry = sl.n;
-                    csrc = sl.h.p;
-                }
-            } catch (...) {     // (the event vector, read_parallel's threads)
-                r = ss_fail(SS_ENOMEM, "FASTQ reader: out of host memory");
-            }
-            if (!r) r = ss_check(hipEventRecord(sl.done, g->fq_copy), "ingest fastq event");
-            sl.rc = r;
-            if (r) sl.err = ss_last_error_string();
-            {
-                std::lock_guard<std::mutex> lk(mu);
-                state[k & 1] = 1;
-            }
-            cv.notify_all();
-            if (r || sl.at_eof || sl.n == 0) return;
-            csrc = sl.h.p + sl.use;
-            carry = sl.n - sl.use;
-        }
-    };
-    // a range that fits one chunk has nothing to overlap: it is read on this thread (no thread start)
-    // unless the reader is to run on the GPU's NUMA node (the caller's affinity is left alone)
-    std::thread rd;
-    if (size - begin <= cap0 && g->fq_cpus.empty()) {
-        reader();
-    } else {
-        try {
-            rd = std::thread(reader);
-        } catch (...) {
-            close(fd);
-            return ss_fail(SS_EHIP, "cannot start the FASTQ reader thread");
-        }
-    }
+    // The reader fills chunk k + 1 into slot (k + 1) & 1 and queues its H2D pieces on fq.copy while
+    // this thread indexes and counts chunk k from slot k & 1 on the engine's stream.  A slot goes back
+    // to the reader once the engine's stream has finished with it.
+    FqReader rd(fq, {fd.v, begin, size, cap0, threads, &fq.ms[0]}, fq.cpus);
     for (uint64_t k = 0; !rc; ++k) {
-        FqSlot& sl = g->fq[k & 1];
-        {
-            std::unique_lock<std::mutex> lk(mu);
-            cv.wait(lk, [&] { return state[k & 1] == 1; });
-        }
-        if (sl.rc) {
-            rc = ss_fail(sl.rc, sl.err.c_str());     // (raised again on this thread: the message is thread-local)
+        const FqChunk& c = rd.acquire(k);
+        if (c.rc) {
+            rc = ss_fail(c.rc, c.err.c_str());     // (raised again on this thread: the message is thread-local)
             break;
         }
-        if (sl.n == 0) break;
-        const uint64_t use = sl.use;
-        const bool at_eof = sl.at_eof;
+        const FqState::Slot& sl = fq.slot[k & 1];
         // index the chunk on the device once its H2D pieces are done (the engine's stream waits for them)
         const auto ti = Clock::now();
-        rc = ss_check(hipStreamWaitEvent(s, sl.done, 0), "ingest fastq wait");
-        uint64_t maxr = use / 16 + 2;
         uint64_t nl = 0, nrec = 0;
-        while (!rc) {
-            const uint64_t wsb = ss_fastq_onepass_ws_bytes(use, maxr);
-            if ((rc = g->fq_ws.ensure(wsb / 8 + 1)) || (rc = g->offs.ensure(maxr)) || (rc = g->dlens.ensure(maxr)) ||
-                (rc = g->fq_aux.ensure(maxr)) || (rc = g->fq_counts.ensure(3)))
-                break;
-            rc = ss_fastq_index_onepass(sl.d.p, use, line0, at_eof ? 1 : 0, g->fq_ws.p, wsb, g->offs.p, g->dlens.p,
-                                        g->fq_aux.p, maxr, g->fq_counts.p, s);
-            if (!rc) rc = ss_check(hipMemcpyAsync(g->h_bad, g->fq_counts.p, 24, hipMemcpyDeviceToHost, s), "ingest fq");
-            if (!rc) rc = ss_check(hipStreamSynchronize(s), "ingest fq");
-            if (rc) break;
-            nl = g->h_bad[0];
-            nrec = g->h_bad[1];
-            if (g->h_bad[2]) {
-                maxr *= 2;
-                continue;
-            }
-            if (nrec <= maxr) break;
-            maxr = nrec;
-        }
+        rc = ss_check(hipStreamWaitEvent(s, sl.done, 0), "ingest fastq wait");
+        if (!rc) rc = index_chunk(g, sl.d.p, c.use, line0, c.at_eof, &nl, &nrec);
         if (rc) break;
-        g->fq_ms[2] += since(ti);
-        for (uint32_t q = 0; q < sl.np; ++q) {     // the pieces' H2D times (all complete: the index synced)
-            float ms = 0;
-            if (hipEventElapsedTime(&ms, sl.ev[2 * q], sl.ev[2 * q + 1]) == hipSuccess) g->fq_ms[1] += ms;
-            else (void)hipGetLastError();
-        }
-        if (!at_eof && g->est_scale == 1.0 && use) g->est_scale = (double)(size - begin) / (double)use;
+        fq.ms[2] += since(ti);
+        fq.ms[1] += fq.pieces_ms(k & 1, c.np);     // (all complete: the index synced)
+        if (!c.at_eof && g->est_scale == 1.0 && c.use) g->est_scale = (double)(size - begin) / (double)c.use;
         const auto tc = Clock::now();
-        rc = process_chunk(g, {sl.d.p, g->offs.p, g->dlens.p, use, nrec, 0, nullptr, sl.h.p});
-        g->fq_ms[3] += since(tc);
+        rc = process_chunk(g, {sl.d.p, g->offs.p, g->dlens.p, c.use, nrec, 0, nullptr, sl.h.p});
+        fq.ms[3] += since(tc);
         if (rc) break;
         line0 += nl;
-        if (at_eof || g->bad_index != kNoSlot) break;
+        if (c.at_eof || g->bad_index != kNoSlot) break;
         if ((rc = ss_check(hipStreamSynchronize(s), "ingest chunk"))) break;
-        {
-            std::lock_guard<std::mutex> lk(mu);
-            state[k & 1] = 0;
-        }
-        cv.notify_all();
+        rd.release(k);
     }
-    {
-        std::lock_guard<std::mutex> lk(mu);
-        stop = true;
-    }
-    cv.notify_all();
-    if (rd.joinable()) rd.join();
-    const int rc2 = ss_check(hipStreamSynchronize(g->fq_copy), "ingest fastq copies");
+    rd.stop();
+    const int rc2 = ss_check(hipStreamSynchronize(fq.copy), "ingest fastq copies");
     if (!rc) rc = rc2;
-    close(fd);
     if (!rc) rc = ss_check(hipStreamSynchronize(s), "ingest fastq");
     if (h_nseqs) *h_nseqs = g->nreads - seqs0;
     return rc;
@@ -2378,18 +2268,18 @@ static int finish_impl(ss_ingest* g, uint64_t* h_nkeys, uint64_t* h_nwords);
 int ss_ingest_finish(ss_ingest* g, uint64_t* h_nkeys, uint64_t* h_nwords) {
     const auto t0 = std::chrono::steady_clock::now();
     const int rc = finish_impl(g, h_nkeys, h_nwords);
-    if (g) g->fq_ms[4] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (g) g->fq.ms[4] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return rc;
 }
 
 int ss_ingest_fastq_stages(ss_ingest* g, double* h_ms, uint64_t* h_h2d_bytes) {
     if (!g || !h_ms || !h_h2d_bytes) return ss_fail(SS_EARG, "null argument");
     for (int i = 0; i < 5; ++i) {
-        h_ms[i] = g->fq_ms[i];
-        g->fq_ms[i] = 0;
+        h_ms[i] = g->fq.ms[i];
+        g->fq.ms[i] = 0;
     }
-    *h_h2d_bytes = g->fq_h2d_bytes;
-    g->fq_h2d_bytes = 0;
+    *h_h2d_bytes = g->fq.h2d_bytes;
+    g->fq.h2d_bytes = 0;
     return SS_OK;
 }
 

@@ -17,7 +17,6 @@
 // staging copies and the kernel bounds the rate: this is the PCIe-inclusive path, never the
 // device-resident roofline number.
 #include <ctype.h>
-#include <pthread.h>
 #include <sched.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -25,92 +24,13 @@
 
 #include <algorithm>
 #include <chrono>
-#include <condition_variable>
-#include <mutex>
 #include <new>
-#include <thread>
 #include <vector>
 
+#include "host_threads.h"
 #include "ss_internal.h"
 
 namespace {
-
-// Fixed pool of copy threads: copy() splits one memcpy into page-aligned parts, the calling
-// thread takes part 0 and blocks until every part is done.
-class CopyPool {
-  public:
-    // cpus: where the workers run (worker i on cpus[i % size]); empty = wherever the OS puts them
-    CopyPool(int nthreads, const std::vector<int>& cpus) {
-        for (int i = 0; i < nthreads; ++i) {
-            th_.emplace_back([this, i] { worker(i); });
-            if (!cpus.empty()) {
-                cpu_set_t set;
-                CPU_ZERO(&set);
-                CPU_SET(cpus[i % cpus.size()], &set);
-                (void)pthread_setaffinity_np(th_.back().native_handle(), sizeof(set), &set);
-            }
-        }
-    }
-    ~CopyPool() {
-        {
-            std::lock_guard<std::mutex> g(mu_);
-            stop_ = true;
-        }
-        cv_.notify_all();
-        for (auto& t : th_) t.join();
-    }
-    void copy(void* dst, const void* src, size_t n) {
-        const int parts = (int)th_.size() + 1;
-        if (n < (size_t(4) << 20) || parts == 1) {
-            memcpy(dst, src, n);
-            return;
-        }
-        {
-            std::lock_guard<std::mutex> g(mu_);
-            dst_ = (char*)dst;
-            src_ = (const char*)src;
-            n_ = n;
-            parts_ = parts;
-            pending_ = parts - 1;
-            ++gen_;
-        }
-        cv_.notify_all();
-        run_part(0);
-        std::unique_lock<std::mutex> lk(mu_);
-        done_.wait(lk, [this] { return pending_ == 0; });
-    }
-
-  private:
-    void run_part(int p) {
-        const size_t per = ((n_ + parts_ - 1) / parts_ + 4095) & ~size_t(4095);
-        const size_t a = std::min(n_, per * p), b = std::min(n_, a + per);
-        if (b > a) memcpy(dst_ + a, src_ + a, b - a);
-    }
-    void worker(int i) {
-        uint64_t seen = 0;
-        for (;;) {
-            {
-                std::unique_lock<std::mutex> lk(mu_);
-                cv_.wait(lk, [&] { return stop_ || gen_ != seen; });
-                if (stop_) return;
-                seen = gen_;
-            }
-            run_part(i + 1);
-            std::lock_guard<std::mutex> g(mu_);
-            if (--pending_ == 0) done_.notify_one();
-        }
-    }
-    std::vector<std::thread> th_;
-    std::mutex mu_;
-    std::condition_variable cv_, done_;
-    uint64_t gen_ = 0;
-    int pending_ = 0;
-    bool stop_ = false;
-    char* dst_ = nullptr;
-    const char* src_ = nullptr;
-    size_t n_ = 0;
-    int parts_ = 1;
-};
 
 struct Slot {
     uint8_t* h_in = nullptr;    // pinned staging (pageable user input)
@@ -461,7 +381,10 @@ int ss_stager_create(int device, uint64_t chunk_bytes, uint32_t nslots, uint32_t
     }
     st->copy_threads = (int)copy_threads;
     const std::vector<int> cpus = placement(st);
-    st->pool = new (std::nothrow) CopyPool((int)copy_threads, cpus);
+    try {
+        st->pool = new CopyPool((int)copy_threads, cpus);     // (host_threads.h)
+    } catch (...) {     // no memory, or a worker thread that could not start
+    }
     if (!st->pool) {
         free_stager(st);
         return ss_fail(SS_ENOMEM, "copy pool");

@@ -383,6 +383,26 @@ def test_fastq_split_host(tmp_path):
                 assert l0[k] == data[:bs[k]].count(b"\n"), (trial, parts, k)
 
 
+def _h2d_model(data, chunk):
+    """The bytes the reader ring copies to the device for `data` in chunks of `chunk` bytes: a slot
+    holds the carry (the bytes after the previous chunk's last newline) and then file bytes up to its
+    capacity; a slot without a newline doubles the capacity and is sent again whole, as the carry."""
+    size, pos, carry, total = len(data), 0, 0, 0
+    cap = max(16, min(chunk, size + 16))
+    while pos < size:
+        want = min(cap - carry, size - pos)
+        n, pos = carry + want, pos + want        # the slot now holds data[pos - n:pos]
+        total += n
+        nl = data.rfind(b"\n", pos - n, pos)
+        if pos >= size:
+            break
+        if nl < 0:
+            cap, carry = 2 * cap, n
+        else:
+            carry = pos - (nl + 1)
+    return total
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("chunk", [0, 4096])
 def test_fastq_gpu_stage_split(gpu, tmp_path, chunk):
@@ -406,7 +426,7 @@ def test_fastq_gpu_stage_split(gpu, tmp_path, chunk):
     if chunk == 0:
         assert s0["h2d_bytes"] == len(data)
     else:
-        assert len(data) <= s0["h2d_bytes"] < 2 * len(data)
+        assert s0["h2d_bytes"] == _h2d_model(data, chunk)
 
 
 @pytest.mark.gpu
@@ -425,9 +445,13 @@ def test_fastq_gpu_reader_ring(gpu, tmp_path):
     p = tmp_path / "ring.fq"
     p.write_text("".join(recs))
     h = sq.read_and_count_fastq(str(p), device="host")
+    from shortseq_amd import _shortseq
+    data = p.read_bytes()
     for chunk in (1024, 4096, 1 << 16):
         d = sq.read_and_count_fastq(str(p), device="cuda", _chunk_bytes=chunk)
         assert _items(d) == _items(h), chunk
+        # the slots grew at 1024 and 4096 (headers of 2000 to 6000 bytes): each grow's resend counted
+        assert _shortseq.fastq_stage_times()[0]["h2d_bytes"] == _h2d_model(data, chunk), chunk
     recs[300] = "@bad\nACGTZACGT\n+\nIIIIIIIII\n"
     p.write_text("".join(recs))
     with pytest.raises(Exception) as eh:

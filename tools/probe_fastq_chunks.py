@@ -64,5 +64,5 @@ for mult in mults:
         sp = " ".join(f"{k[:-3]} {st[k]:.1f}" for k in ("read_ms", "h2d_dev_ms", "index_ms", "count_ms", "finish_ms",
                                                          "reduce_and_dict_ms") if k in st)
         print(f"{name} chunk {c >> 20 if c else 'default':>7} MB: {np.median(ts[c]) * 1e3:7.1f} ms "
-              f"(min {min(ts[c]) * 1e3:.1f})  [{sp}]", flush=True)
+              f"(min {min(ts[c]) * 1e3:.1f})  [{sp}] h2d_bytes {st.get('h2d_bytes')}", flush=True)
     os.remove(path)
