@@ -211,8 +211,9 @@ int ss_hamming_all_pairs_ex(const uint64_t* d_words, uint64_t n, uint32_t L, uin
  * offsets; the block walks column chunks from its own tile to its last row's group end, each wave only
  * over [its first row + 1, its last row's group end).  Every pair of a group is checked (bit-plane
  * VALU form at every L): no MFMA tiles and no pigeonhole form inside groups -- for ONE group of 10^5 or
- * more rows ss_hamming_all_pairs is the tool.  Also not provided: UMI-tools' `adjacency` method and a
- * grouped form of the whitelist match (ss_hamming_nearest).  tiles_per_launch (_ex; a test hook): row tiles per
+ * more rows ss_hamming_all_pairs is the tool.  All three methods of ss_cluster_pairs, `adjacency`
+ * included, run on the grouped pair list as it stands.  Not provided: a grouped form of the whitelist
+ * match (ss_hamming_nearest).  tiles_per_launch (_ex; a test hook): row tiles per
  * kernel launch, 0 = the library's 2^23 (larger values are clamped to it); the results do not depend on it.
  * Malformed offsets are NOT detected on the device: the kernel still never reads or writes outside the
  * arrays (every end is clamped to n, an end <= i means "no partners", no index >= n is written to
@@ -298,24 +299,39 @@ int ss_host_hamming_nearest(const uint64_t* h_q, uint64_t nq, uint32_t q_wpr, co
  *                both directions may hold); a node's representative is the lowest-rank node among
  *                itself and its directed ancestors, which is the group UMI-tools' count-ordered BFS
  *                with first-observation-wins puts it in.
- * UMI-tools' `adjacency` method (a sequential greedy cover) is not provided.
+ *   ADJACENCY:   per connected component, the leads are the shortest prefix of its nodes in rank
+ *                order whose members and their neighbours cover the component; a lead represents
+ *                itself, any other node goes to its lowest-rank neighbour (a lead, and the first lead
+ *                in order that reaches it: UMI-tools' walk over the leads).  In ranks, without the
+ *                sequence: (1) cover[v] = min(rank[v], rank[u] over v's neighbours u); (2) comp[v] =
+ *                the lowest rank in v's component, as COMPONENTS; (3) thr[c] = max cover[v] over
+ *                comp[v] == c; (4) v leads iff rank[v] <= thr[comp[v]], rep[v] = v for a lead and
+ *                order[cover[v]] otherwise.  Counts enter only through d_order (and d_sums).
+ *                Tie rule: UMI-tools leaves nodes of equal count to set iteration order; here they
+ *                rank by ascending index, as under the other methods.
+ * The method ids are 0, 1 and 3: the value 2 is not a method and stays SS_EARG.
  * Outputs: d_rep[v] = v's representative; d_sizes / d_sums (nullable; d_sums needs d_counts): a
  * cluster's size and u64 count sum at its representative's index, 0 elsewhere; *d_nclusters.
  * ss_cluster_pairs allocates no device memory: the caller supplies d_ws (8-B aligned,
- * ss_cluster_ws_bytes(n, m) bytes).  It is NOT capturable and not asynchronous: rounds (a pass over the
+ * ss_cluster_ws_bytes_method(n, m, method) bytes: for COMPONENTS and DIRECTIONAL that is
+ * ss_cluster_ws_bytes(n, m); ADJACENCY adds three u32 [n] arrays behind that layout).  It is NOT capturable and not asynchronous: rounds (a pass over the
  * pairs, a pass over the nodes) repeat until one lowers no label, and the host reads that flag once per
  * round, synchronising with `stream` (through a 16-B pinned word per host thread, made at the thread's
  * first call; SS_ENOMEM if that fails); on a capturing stream it returns SS_EARG.  *h_rounds (nullable)
- * = rounds run, the last, idle one included (0 when m = 0).  The outputs are queued on `stream`.
+ * = rounds run, the last, idle one included (0 when m = 0); ADJACENCY runs the rounds of COMPONENTS,
+ * one pass over the pairs before them and one over the nodes after them.  The outputs are queued on `stream`.
  * SS_EARG: n >= 2^32, a workspace too small, DIRECTIONAL or d_sums without d_counts (n > 0), an unknown
  * method, or a pair naming a node >= n (never dereferenced: the pair is skipped, the call returns after
  * its first round and the outputs are unspecified).
- * ss_host_cluster_pairs: the same function in plain C++ on host arrays (union-find / a worklist), for
+ * ss_host_cluster_pairs: the same function in plain C++ on host arrays (union-find / a worklist /
+ * union-find and the four steps), for
  * small inputs and hosts without a GPU; the same SS_EARG cases, checked before anything is written.
  * ---------------------------------------------------------------------------------------------- */
 #define SS_CLUSTER_COMPONENTS 0u
 #define SS_CLUSTER_DIRECTIONAL 1u
+#define SS_CLUSTER_ADJACENCY 3u
 uint64_t ss_cluster_ws_bytes(uint64_t n, uint64_t m);
+uint64_t ss_cluster_ws_bytes_method(uint64_t n, uint64_t m, uint32_t method);
 int ss_cluster_pairs(const uint32_t* d_pairs, uint64_t m, uint64_t n, const uint64_t* d_counts, const uint32_t* d_order,
                      uint32_t method, void* d_ws, uint64_t ws_bytes, uint32_t* d_rep, uint32_t* d_sizes, uint64_t* d_sums,
                      uint64_t* d_nclusters, uint32_t* h_rounds, void* stream);

@@ -90,6 +90,7 @@ SIGNATURES = [
     ("ss_hamming_nearest_ex", C.c_int, [_P, _U64, _U32, _P, _U64, _U32, _U32, _U32, _P, _P, _P, _P, _U64, _U32, _P]),
     ("ss_host_hamming_nearest", C.c_int, [_P, _U64, _U32, _P, _U64, _U32, _U32, _U32, _P, _P, _P]),
     ("ss_cluster_ws_bytes", _U64, [_U64, _U64]),
+    ("ss_cluster_ws_bytes_method", _U64, [_U64, _U64, _U32]),
     ("ss_cluster_pairs", C.c_int, [_P, _U64, _U64, _P, _P, _U32, _P, _U64, _P, _P, _P, _P, C.POINTER(C.c_uint32), _P]),
     ("ss_host_cluster_pairs", C.c_int, [_P, _U64, _U64, _P, _P, _U32, _P, _P, _P, _P]),
     ("ss_fastq_scan_ws_bytes", _U64, [_U64]),

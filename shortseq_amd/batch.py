@@ -673,14 +673,20 @@ def hamming_nearest(queries: torch.Tensor, refs: torch.Tensor, L: int, max_dist:
     return widen(idx, True), widen(dist, True), None if nbest is None else widen(nbest, False)
 
 
-CLUSTER_METHODS = {"cluster": 0, "directional": 1}
+CLUSTER_METHODS = {"cluster": 0, "directional": 1, "adjacency": 3}    # SS_CLUSTER_*; 2 is not a method
 
 
 def cluster_pairs(pairs: torch.Tensor, n: int, counts: Optional[torch.Tensor] = None, method: str = "directional",
                   want_sums: bool = True):
     """Group n nodes (distinct UMIs) by an undirected pair list, as UMI-tools' `cluster` (connected
-    components) or `directional` (edge u -> v iff c[u] >= 2 c[v] - 1) method (ss_cluster_pairs; the
-    `adjacency` method, a sequential greedy cover, is not provided).  pairs: int32 [m, 2] on the
+    components), `directional` (edge u -> v iff c[u] >= 2 c[v] - 1) or `adjacency` method
+    (ss_cluster_pairs).  `adjacency`: per component the leads are the shortest count-ordered prefix
+    whose nodes and their neighbours cover it; a lead represents itself, any other node goes to its
+    highest-ranked neighbour.  With rank = position by count descending, ties by index, that is
+    (1) cover[v] = min rank over v and its neighbours, (2) comp[v] = the lowest rank in v's component,
+    (3) thr[c] = max cover over component c, (4) v leads iff rank[v] <= thr[comp[v]], else it joins
+    the node of rank cover[v].  UMI-tools leaves equal counts to set iteration order; here ties go by
+    ascending index under every method.  pairs: int32 [m, 2] on the
     device, i < j, any order (hamming_all_pairs' pair output); counts: int64 [n] or None (required for
     "directional").  -> (rep int64 [n]: every node's representative, reps int64 [k]: the
     representatives by count descending, ties by index, sizes int64 [k], sums int64 [k] of the
@@ -699,7 +705,7 @@ def cluster_pairs(pairs: torch.Tensor, n: int, counts: Optional[torch.Tensor] = 
         order = torch.sort(counts, descending=True, stable=True).indices.to(torch.int32)
     sums_on = want_sums and counts is not None
     L_ = lib()
-    ws_bytes = int(L_.ss_cluster_ws_bytes(n, m))
+    ws_bytes = int(L_.ss_cluster_ws_bytes_method(n, m, CLUSTER_METHODS[method]))
     ws = torch.empty((ws_bytes + 7) // 8, dtype=torch.int64, device=dev)
     rep = torch.empty(n, dtype=torch.int32, device=dev)
     sizes = torch.empty(n, dtype=torch.int32, device=dev)
@@ -807,7 +813,9 @@ def umi_cluster_grouped(words: torch.Tensor, L: int, max_dist: int, group_offset
     and one more run with exactly the total when that was too small), then cluster_pairs on the global
     indices: no pair crosses a group, so no cluster does, and rows of a group being contiguous, the
     (count descending, index ascending) rank restricted to a group is the group's own, so every
-    representative is the one umi_cluster on that group alone would name.
+    representative is the one umi_cluster on that group alone would name.  "adjacency" needs nothing
+    else: the global rank restricted to a group's contiguous rows is the group's own order, so leads
+    and groups are those of a per-group run.
     -> cluster_pairs' tuple plus the pair total; all indices are global rows.  A cluster's group:
     ``torch.bucketize(reps, offsets[1:], right=True)``."""
     _require_cuda(words, "words")

@@ -1,5 +1,6 @@
 // ss_cluster.hip — UMI clustering over the pair list of ss_hamming_all_pairs*: the `cluster`
-// (connected components) and `directional` methods of UMI-tools as one min-label fixpoint.
+// (connected components) and `directional` methods of UMI-tools as one min-label fixpoint, and its
+// `adjacency` method as a min-rank cover on top of the `cluster` fixpoint (below, "Adjacency").
 //
 // order = the nodes by count descending, ties by index (identity without d_order); rank = its inverse.
 // label[v] starts at rank[v]; a round is a hook pass over the pairs (label[v] = min(label[v], label[u])
@@ -16,6 +17,21 @@
 // labels no kernel has written since the last kernel boundary, so every load in it was fresh and the
 // fixpoint test is sound.  The round loop runs on the host (one 16-B read of the changed and bad-index
 // flags per round through a pinned word); there is no grid-wide barrier.
+//
+// Adjacency (UMI-tools: per component, the shortest count-ordered prefix whose nodes and their
+// neighbours cover the component are the leads; a lead's group is itself and its neighbours that are
+// neither leads nor taken by an earlier lead).  In ranks:
+//   1. cover[v] = min(rank[v], rank[u] over v's neighbours u)      one pass over the pairs, before the rounds
+//   2. comp[v]  = the lowest rank in v's component                 the `cluster` fixpoint, unchanged
+//   3. thr[c]   = max cover[v] over comp[v] == c                   one pass over the nodes
+//   4. v leads iff rank[v] <= thr[comp[v]]; rep[v] = v for a lead, order[cover[v]] otherwise
+// A prefix of ranks 0 .. i covers a component iff every node has a closed-neighbourhood member of rank
+// <= i, so the shortest covering prefix ends at rank thr; global ranks keep the order inside a
+// component.  A non-lead's lowest-rank neighbour has rank cover[v] <= thr: a lead, and the first lead in
+// order that reaches v.  Every step is a min or a max over integers.  cover is lowered only by
+// atomicMin and thr raised only by atomicMax; the plain read in front of either may be stale, which is
+// larger (cover) or smaller (thr) than the true value, so the atomic still runs where it matters.
+// Kernel boundaries separate the steps: after its own pass each array is read by plain loads.
 #include <stdint.h>
 
 #include <vector>
@@ -36,16 +52,24 @@ struct ClWs {
     uint32_t* hdr;
     uint32_t* label;
     unsigned long long* bits;   // per 64 body units (128 pairs): 4 ballots, bit b of a unit in word b
+    uint32_t* cover;            // adjacency only, after the layout of the other methods: u32 [n] each
+    uint32_t* thr;
+    uint32_t* rank;
 };
 
 inline uint64_t cl_label_bytes(uint64_t n) { return (4 * n + 63) / 64 * 64; }
 inline uint64_t cl_bits_bytes(uint64_t m) { return ((m / 2 + 63) / 64) * 32 + 32; }
 
-inline ClWs cl_ws(void* d_ws, uint64_t n) {
+inline uint64_t cl_base_bytes(uint64_t n, uint64_t m) { return kClHdrBytes + cl_label_bytes(n) + cl_bits_bytes(m); }
+
+inline ClWs cl_ws(void* d_ws, uint64_t n, uint64_t m) {
     ClWs w;
     w.hdr = (uint32_t*)d_ws;
     w.label = (uint32_t*)((char*)d_ws + kClHdrBytes);
     w.bits = (unsigned long long*)((char*)d_ws + kClHdrBytes + cl_label_bytes(n));
+    w.cover = (uint32_t*)((char*)d_ws + cl_base_bytes(n, m));      // only valid in an adjacency workspace
+    w.thr = (uint32_t*)((char*)w.cover + cl_label_bytes(n));
+    w.rank = (uint32_t*)((char*)w.thr + cl_label_bytes(n));
     return w;
 }
 
@@ -182,6 +206,44 @@ __global__ __launch_bounds__(kClT) void k_cl_shortcut(const uint32_t* __restrict
 // one word (measured: 1M nodes, 0.8M in one component, 12 of the call's 13 ms): the lanes of a wave that
 // share a representative add once.
 constexpr int kPeel = 4;
+// One wave's 64 nodes (lane `on`: node v with representative r and count c; called by whole waves):
+// the clusters counted, sizes and sums added.
+__device__ __forceinline__ void cl_accumulate(uint32_t lane, bool on, uint64_t v, uint32_t r, unsigned long long c,
+                                              uint32_t* __restrict__ sizes, unsigned long long* __restrict__ sums,
+                                              unsigned long long* __restrict__ nclusters) {
+    const unsigned long long roots = __ballot(on && r == (uint32_t)v);
+    if (lane == 0 && roots) atomicAdd(nclusters, (unsigned long long)__popcll(roots));
+    if (!sizes && !sums) return;
+    // up to kPeel representatives per wave are summed in the wave and added once (rem and every
+    // branch on it are wave-uniform); what is left after that adds per lane
+    unsigned long long rem = __ballot(on);
+    bool mine = on;
+    for (int it = 0; it < kPeel && rem; ++it) {
+        const uint32_t rl = (uint32_t)__shfl((int)r, __ffsll((long long)rem) - 1);
+        const bool in = mine && r == rl;
+        const unsigned long long mask = __ballot(in);
+        rem &= ~mask;
+        if (__popcll(mask) == 1) continue;      // its one lane adds below
+        unsigned long long s = in ? c : 0;
+        if (sums) {
+            for (int o = 32; o; o >>= 1) {
+                const uint32_t lo = (uint32_t)__shfl_down((int)(uint32_t)s, o);
+                const uint32_t hi = (uint32_t)__shfl_down((int)(uint32_t)(s >> 32), o);
+                s += (unsigned long long)hi << 32 | lo;
+            }
+        }
+        if (lane == 0) {
+            if (sizes) atomicAdd(&sizes[rl], (uint32_t)__popcll(mask));
+            if (sums) atomicAdd(&sums[rl], s);
+        }
+        mine = mine && !in;
+    }
+    if (mine) {
+        if (sizes) atomicAdd(&sizes[r], 1u);
+        if (sums) atomicAdd(&sums[r], c);
+    }
+}
+
 __global__ __launch_bounds__(kClT) void k_cl_finish(const uint32_t* __restrict__ order, const uint32_t* __restrict__ label,
                                                     const unsigned long long* __restrict__ counts, uint64_t n,
                                                     uint32_t* __restrict__ rep, uint32_t* __restrict__ sizes,
@@ -200,37 +262,132 @@ __global__ __launch_bounds__(kClT) void k_cl_finish(const uint32_t* __restrict__
             rep[v] = r;
             if (sums) c = counts[v];
         }
-        const unsigned long long roots = __ballot(on && r == (uint32_t)v);
-        if (lane == 0 && roots) atomicAdd(nclusters, (unsigned long long)__popcll(roots));
-        if (!sizes && !sums) continue;
-        // up to kPeel representatives per wave are summed in the wave and added once (rem and every
-        // branch on it are wave-uniform); what is left after that adds per lane
-        unsigned long long rem = __ballot(on);
-        bool mine = on;
+        cl_accumulate(lane, on, v, r, c, sizes, sums, nclusters);
+    }
+}
+
+// ---- adjacency ------------------------------------------------------------------------------------
+// After k_cl_init (label = rank): cover[v] = rank[v], the rank kept for the finish (label loses it in
+// the rounds; null without an order: rank[v] = v), thr[c] = c (a component's lowest rank c is its
+// root's own cover, so the maximum is never below it: nodes whose cover is c never need the atomic).
+__global__ __launch_bounds__(kClT) void k_cl_adj_init(const uint32_t* __restrict__ label, uint64_t n,
+                                                      uint32_t* __restrict__ cover, uint32_t* __restrict__ thr,
+                                                      uint32_t* __restrict__ rank) {
+    const uint64_t stride = (uint64_t)gridDim.x * kClT;
+    for (uint64_t v = (uint64_t)blockIdx.x * kClT + threadIdx.x; v < n; v += stride) {
+        const uint32_t r = label[v];
+        cover[v] = r;
+        if (rank) rank[v] = r;
+        thr[v] = (uint32_t)v;
+    }
+}
+
+// cover[dst] = min(cover[dst], rs) where the value read says that lowers it (cl_lower's idiom)
+__device__ __forceinline__ void cl_cover_lower(uint32_t* cover, uint32_t dst, uint32_t rs) {
+    if (rs < cover[dst]) atomicMin(&cover[dst], rs);
+}
+
+// one pair (i, j): each end's cover takes the other's rank; a node >= n is never dereferenced
+__device__ __forceinline__ void cl_cover_pair(const uint32_t* __restrict__ rank, uint32_t* cover, uint32_t i, uint32_t j,
+                                              uint64_t n, bool& bad) {
+    if (i >= n || j >= n) {
+        bad = true;
+        return;
+    }
+    const uint32_t ri = rank[i], rj = rank[j];
+    cl_cover_lower(cover, j, ri);
+    cl_cover_lower(cover, i, rj);
+}
+
+// Cover pass (step 1), over the hook's stream shape: the unaligned head pair, nu 16-B body units, the
+// odd tail pair.  Runs before the first round, while label still equals rank and no kernel writes it.
+__global__ __launch_bounds__(kClT) void k_cl_cover(const uint32_t* __restrict__ pairs, uint32_t head, uint64_t nu,
+                                                   uint32_t tail, uint64_t n, const uint32_t* __restrict__ rank,
+                                                   uint32_t* __restrict__ cover, uint32_t* __restrict__ hdr) {
+    const uint64_t stride = (uint64_t)gridDim.x * kClT;
+    const uint4* body = (const uint4*)(pairs + 2 * head);
+    bool bad = false;
+    for (uint64_t u = (uint64_t)blockIdx.x * kClT + threadIdx.x; u < nu; u += stride) {
+        const uint4 p = body[u];
+        cl_cover_pair(rank, cover, p.x, p.y, n, bad);
+        cl_cover_pair(rank, cover, p.z, p.w, n, bad);
+    }
+    if (blockIdx.x == 0 && threadIdx.x < 2) {   // thread 0: the unaligned first pair, thread 1: the odd last one
+        const bool is_tail = threadIdx.x == 1;
+        if (is_tail ? tail : head) {
+            const uint32_t* q = is_tail ? pairs + 2 * ((uint64_t)head + 2 * nu) : pairs;
+            cl_cover_pair(rank, cover, q[0], q[1], n, bad);
+        }
+    }
+    if (bad) atomicOr(&hdr[kHdrBad], 1u);
+}
+
+// thr[c] = max(thr[c], x) where the value read says that raises it
+__device__ __forceinline__ void cl_raise(uint32_t* thr, uint32_t c, uint32_t x) {
+    if (x > thr[c]) atomicMax(&thr[c], x);
+}
+
+// Threshold pass (step 3), after the fixpoint (label = comp).  A giant component sends every node to
+// one word (k_cl_finish's note): up to kPeel components per wave take their maximum in the wave and
+// one lane raises thr, what is left raises per lane; either only where the value read is lower.
+__global__ __launch_bounds__(kClT) void k_cl_thr(const uint32_t* __restrict__ label, const uint32_t* __restrict__ cover,
+                                                 uint64_t n, uint32_t* __restrict__ thr) {
+    const uint32_t lane = threadIdx.x & 63;
+    const uint64_t stride = (uint64_t)gridDim.x * kClT;
+    for (uint64_t base = (uint64_t)blockIdx.x * kClT + (threadIdx.x & ~63u); base < n; base += stride) {
+        const uint64_t v = base + lane;
+        uint32_t c = 0, x = 0;
+        if (v < n) {
+            c = label[v];
+            x = cover[v];
+        }
+        bool mine = v < n && x > c;             // cover == comp: thr[c] started there
+        unsigned long long rem = __ballot(mine);
         for (int it = 0; it < kPeel && rem; ++it) {
-            const uint32_t rl = (uint32_t)__shfl((int)r, __ffsll((long long)rem) - 1);
-            const bool in = mine && r == rl;
+            const uint32_t cl = (uint32_t)__shfl((int)c, __ffsll((long long)rem) - 1);
+            const bool in = mine && c == cl;
             const unsigned long long mask = __ballot(in);
             rem &= ~mask;
-            if (__popcll(mask) == 1) continue;      // its one lane adds below
-            unsigned long long s = in ? c : 0;
-            if (sums) {
-                for (int o = 32; o; o >>= 1) {
-                    const uint32_t lo = (uint32_t)__shfl_down((int)(uint32_t)s, o);
-                    const uint32_t hi = (uint32_t)__shfl_down((int)(uint32_t)(s >> 32), o);
-                    s += (unsigned long long)hi << 32 | lo;
-                }
+            if (__popcll(mask) == 1) continue;      // its one lane raises below
+            uint32_t mx = in ? x : 0;
+            for (int o = 32; o; o >>= 1) {
+                const uint32_t other = (uint32_t)__shfl_down((int)mx, o);
+                mx = other > mx ? other : mx;
             }
-            if (lane == 0) {
-                if (sizes) atomicAdd(&sizes[rl], (uint32_t)__popcll(mask));
-                if (sums) atomicAdd(&sums[rl], s);
-            }
+            if (lane == 0) cl_raise(thr, cl, mx);
             mine = mine && !in;
         }
-        if (mine) {
-            if (sizes) atomicAdd(&sizes[r], 1u);
-            if (sums) atomicAdd(&sums[r], c);
+        if (mine) cl_raise(thr, c, x);
+    }
+}
+
+// Finish (step 4): a lead (rank[v] <= thr[comp[v]]) represents itself, any other node goes to its
+// lowest-rank neighbour order[cover[v]]; then as k_cl_finish.
+__global__ __launch_bounds__(kClT) void k_cl_adj_finish(const uint32_t* __restrict__ order, const uint32_t* __restrict__ label,
+                                                        const uint32_t* __restrict__ cover, const uint32_t* __restrict__ thr,
+                                                        const uint32_t* __restrict__ rank,
+                                                        const unsigned long long* __restrict__ counts, uint64_t n,
+                                                        uint32_t* __restrict__ rep, uint32_t* __restrict__ sizes,
+                                                        unsigned long long* __restrict__ sums,
+                                                        unsigned long long* __restrict__ nclusters) {
+    const uint32_t lane = threadIdx.x & 63;
+    const uint64_t stride = (uint64_t)gridDim.x * kClT;
+    for (uint64_t base = (uint64_t)blockIdx.x * kClT + (threadIdx.x & ~63u); base < n; base += stride) {
+        const uint64_t v = base + lane;
+        const bool on = v < n;
+        uint32_t r = 0;
+        unsigned long long c = 0;
+        if (on) {
+            const uint32_t rk = rank ? rank[v] : (uint32_t)v;
+            r = (uint32_t)v;
+            if (rk > thr[label[v]]) {
+                const uint32_t cv = cover[v];
+                r = order ? order[cv] : cv;
+            }
+            rep[v] = r;
+            if (sums) c = counts[v];
         }
+        cl_accumulate(lane, on, v, r, c, sizes, sums, nclusters);
     }
 }
 
@@ -243,7 +400,8 @@ uint32_t* cl_pinned_hdr() {
 
 int cl_check_args(uint64_t n, const void* counts, uint32_t method, const void* sums) {
     if (n >= (1ull << 32)) return ss_fail(SS_EARG, "cluster: n must be < 2^32");
-    if (method != SS_CLUSTER_COMPONENTS && method != SS_CLUSTER_DIRECTIONAL) return ss_fail(SS_EARG, "cluster: unknown method");
+    if (method != SS_CLUSTER_COMPONENTS && method != SS_CLUSTER_DIRECTIONAL && method != SS_CLUSTER_ADJACENCY)
+        return ss_fail(SS_EARG, "cluster: unknown method");
     // n = 0: an empty array may well be a null pointer
     if (method == SS_CLUSTER_DIRECTIONAL && !counts && n) return ss_fail(SS_EARG, "cluster: directional needs counts");
     if (sums && !counts && n) return ss_fail(SS_EARG, "cluster: sums need counts");
@@ -255,7 +413,12 @@ int cl_check_args(uint64_t n, const void* counts, uint32_t method, const void* s
 extern "C" {
 
 // header 64 B | label u32 [n] (to 64 B) | direction bits, 32 B per 128 pairs
-uint64_t ss_cluster_ws_bytes(uint64_t n, uint64_t m) { return kClHdrBytes + cl_label_bytes(n) + cl_bits_bytes(m); }
+uint64_t ss_cluster_ws_bytes(uint64_t n, uint64_t m) { return cl_base_bytes(n, m); }
+
+// adjacency: the same, then cover, thr and rank, u32 [n] (to 64 B) each
+uint64_t ss_cluster_ws_bytes_method(uint64_t n, uint64_t m, uint32_t method) {
+    return cl_base_bytes(n, m) + (method == SS_CLUSTER_ADJACENCY ? 3 * cl_label_bytes(n) : 0);
+}
 
 int ss_cluster_pairs(const uint32_t* d_pairs, uint64_t m, uint64_t n, const uint64_t* d_counts, const uint32_t* d_order,
                      uint32_t method, void* d_ws, uint64_t ws_bytes, uint32_t* d_rep, uint32_t* d_sizes, uint64_t* d_sums,
@@ -264,7 +427,7 @@ int ss_cluster_pairs(const uint32_t* d_pairs, uint64_t m, uint64_t n, const uint
     if (rc) return rc;
     if (!d_ws || !d_nclusters || (n && !d_rep) || (m && !d_pairs)) return ss_fail(SS_EARG, "cluster: null buffer");
     if ((((uintptr_t)d_ws) & 7) || (((uintptr_t)d_pairs) & 7)) return ss_fail(SS_EARG, "cluster: d_ws and d_pairs must be 8-B aligned");
-    if (ws_bytes < ss_cluster_ws_bytes(n, m)) return ss_fail(SS_EARG, "cluster: workspace too small");
+    if (ws_bytes < ss_cluster_ws_bytes_method(n, m, method)) return ss_fail(SS_EARG, "cluster: workspace too small");
     hipStream_t s = (hipStream_t)stream;
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(s, &cap) != hipSuccess) {
@@ -275,7 +438,7 @@ int ss_cluster_pairs(const uint32_t* d_pairs, uint64_t m, uint64_t n, const uint
     uint32_t* h_hdr = cl_pinned_hdr();
     if (!h_hdr) return ss_fail(SS_ENOMEM, "cluster: pinned flag word");
 
-    const ClWs w = cl_ws(d_ws, n);
+    const ClWs w = cl_ws(d_ws, n, m);
     const unsigned long long* counts = (const unsigned long long*)d_counts;
     unsigned long long* sums = (unsigned long long*)d_sums;
     unsigned long long* ncl = (unsigned long long*)d_nclusters;
@@ -287,6 +450,14 @@ int ss_cluster_pairs(const uint32_t* d_pairs, uint64_t m, uint64_t n, const uint
     const uint32_t tail = (uint32_t)((m - head) & 1);
     const unsigned gm = cl_grid(nu);
     const bool dir = method == SS_CLUSTER_DIRECTIONAL;
+    const bool adj = method == SS_CLUSTER_ADJACENCY;
+    uint32_t* const rank = d_order ? w.rank : nullptr;
+    if (adj) {
+        hipLaunchKernelGGL(k_cl_adj_init, dim3(gn), dim3(kClT), 0, s, (const uint32_t*)w.label, n, w.cover, w.thr, rank);
+        if (m)
+            hipLaunchKernelGGL(k_cl_cover, dim3(gm), dim3(kClT), 0, s, d_pairs, head, nu, tail, n, (const uint32_t*)w.label,
+                               w.cover, w.hdr);
+    }
     uint32_t rounds = 0;
     while (m) {
         if (!dir)
@@ -308,14 +479,22 @@ int ss_cluster_pairs(const uint32_t* d_pairs, uint64_t m, uint64_t n, const uint
         if (h_hdr[kHdrBad]) return ss_fail(SS_EARG, "cluster: a pair names a node >= n");
         if (!changed) break;
     }
-    hipLaunchKernelGGL(k_cl_finish, dim3(gn), dim3(kClT), 0, s, d_order, (const uint32_t*)w.label, counts, n, d_rep, d_sizes,
-                       sums, ncl);
+    if (adj) {
+        if (m) hipLaunchKernelGGL(k_cl_thr, dim3(gn), dim3(kClT), 0, s, (const uint32_t*)w.label, (const uint32_t*)w.cover, n, w.thr);
+        hipLaunchKernelGGL(k_cl_adj_finish, dim3(gn), dim3(kClT), 0, s, d_order, (const uint32_t*)w.label,
+                           (const uint32_t*)w.cover, (const uint32_t*)w.thr, (const uint32_t*)rank, counts, n, d_rep, d_sizes,
+                           sums, ncl);
+    } else {
+        hipLaunchKernelGGL(k_cl_finish, dim3(gn), dim3(kClT), 0, s, d_order, (const uint32_t*)w.label, counts, n, d_rep,
+                           d_sizes, sums, ncl);
+    }
     if (h_rounds) *h_rounds = rounds;
     return ss_check(hipGetLastError(), "k_cl_init/k_cl_finish");
 }
 
 // The same on the host: union-find keeping each set's lowest rank for `cluster`; for `directional` a
-// worklist over the directed edges (CSR by source) that lowers label[v] to label[u] until nothing moves.
+// worklist over the directed edges (CSR by source) that lowers label[v] to label[u] until nothing moves;
+// for `adjacency` the union-find for the components, then steps 1, 3 and 4 of the note at the top.
 int ss_host_cluster_pairs(const uint32_t* h_pairs, uint64_t m, uint64_t n, const uint64_t* h_counts,
                           const uint32_t* h_order, uint32_t method, uint32_t* h_rep, uint32_t* h_sizes, uint64_t* h_sums,
                           uint64_t* h_nclusters) {
@@ -326,7 +505,7 @@ int ss_host_cluster_pairs(const uint32_t* h_pairs, uint64_t m, uint64_t n, const
         if (h_pairs[e] >= n) return ss_fail(SS_EARG, "cluster: a pair names a node >= n");
     std::vector<uint32_t> label(n);
     for (uint64_t r = 0; r < n; ++r) label[h_order ? h_order[r] : r] = (uint32_t)r;
-    if (method == SS_CLUSTER_COMPONENTS) {
+    if (method != SS_CLUSTER_DIRECTIONAL) {
         std::vector<uint32_t> parent(n);
         for (uint64_t v = 0; v < n; ++v) parent[v] = (uint32_t)v;
         auto find = [&](uint32_t v) {
@@ -343,6 +522,20 @@ int ss_host_cluster_pairs(const uint32_t* h_pairs, uint64_t m, uint64_t n, const
             else parent[a] = b;
         }
         for (uint64_t v = 0; v < n; ++v) h_rep[v] = find((uint32_t)v);
+        if (method == SS_CLUSTER_ADJACENCY) {
+            std::vector<uint32_t> cover(label), thr(n, 0);          // thr at a component's root node
+            for (uint64_t e = 0; e < m; ++e) {
+                const uint32_t i = h_pairs[2 * e], j = h_pairs[2 * e + 1];
+                if (label[j] < cover[i]) cover[i] = label[j];
+                if (label[i] < cover[j]) cover[j] = label[i];
+            }
+            for (uint64_t v = 0; v < n; ++v)
+                if (cover[v] > thr[h_rep[v]]) thr[h_rep[v]] = cover[v];
+            for (uint64_t v = 0; v < n; ++v) {
+                if (label[v] <= thr[h_rep[v]]) h_rep[v] = (uint32_t)v;
+                else h_rep[v] = h_order ? h_order[cover[v]] : cover[v];
+            }
+        }
     } else {
         std::vector<uint64_t> start(n + 1, 0);
         auto edge = [&](uint32_t u, uint32_t v) { return h_counts[u] + 1 >= 2 * h_counts[v]; };

@@ -1,10 +1,15 @@
 """UMI dedup at the drop-in level: group a counter's distinct reads into UMI clusters.
 
 ``dedup(counter)`` takes a ShortSeqCounter (or any mapping ShortSeq -> count) and groups its keys as
-UMI-tools' ``directional`` or ``cluster`` method does: keys of equal length within ``max_dist``
-substitutions are neighbours, and a cluster is named by its highest-count key (ties: the key that
-came first in the mapping).  UMI-tools' ``adjacency`` method, a sequential greedy cover, is not
-provided.  The grouping itself is ss_cluster_pairs / ss_host_cluster_pairs (include/shortseq_amd.h).
+UMI-tools' ``directional``, ``cluster`` or ``adjacency`` method does: keys of equal length within
+``max_dist`` substitutions are neighbours, and a cluster is named by its highest-count key (ties: the
+key that came first in the mapping).  ``adjacency``: in every connected component the leads are the
+shortest count-ordered prefix whose keys and their neighbours cover the component; a lead names its own
+cluster and every other key joins its highest-ranked neighbour.  In ranks (count descending, ties by
+position): cover[v] = the lowest rank among v and its neighbours, thr = the highest cover in v's
+component, v leads iff rank[v] <= thr, else it joins the key of rank cover[v].  UMI-tools leaves keys of
+equal count to set iteration order; here they go by position in the mapping under every method.
+The grouping itself is ss_cluster_pairs / ss_host_cluster_pairs (include/shortseq_amd.h).
 """
 from __future__ import annotations
 
@@ -16,7 +21,8 @@ from ._native import check, lib
 
 __all__ = ["dedup", "dedup_groups", "AUTO_GPU_MIN_KEYS", "AUTO_GPU_MIN_GROUPED_KEYS"]
 
-METHODS = {"cluster": 0, "directional": 1}
+METHODS = {"cluster": 0, "directional": 1, "adjacency": 3}
+GROUPED_METHODS = {"cluster": 0, "directional": 1}     # dedup_groups' own set
 MAX_COUNT = 1 << 62
 
 # device="auto": a length group of at least this many keys goes to the GPU (when there is one).  The
@@ -163,9 +169,11 @@ def dedup_groups(groups, max_dist: int = 1, method: str = "directional", device:
     batch.umi_cluster_grouped call per distinct length, on the host ss_host_hamming_all_pairs_grouped +
     ss_host_cluster_pairs.  Clustering the batch on global row indices names the representatives a run
     per group would ("Grouped all-pairs").  device: "host", "gpu", or "auto" (per length:
-    "gpu" from AUTO_GPU_MIN_GROUPED_KEYS rows on, when a GPU is present)."""
-    if method not in METHODS:
-        raise ValueError(f"method must be one of {sorted(METHODS)}")
+    "gpu" from AUTO_GPU_MIN_GROUPED_KEYS rows on, when a GPU is present).
+    method: "directional" or "cluster".  "adjacency" is refused here (ValueError); the grouped form of it
+    is available through batch.umi_cluster_grouped."""
+    if method not in GROUPED_METHODS:
+        raise ValueError(f"method must be one of {sorted(GROUPED_METHODS)}")
     if device not in ("auto", "host", "gpu"):
         raise ValueError('device must be "auto", "host" or "gpu"')
     labels = list(groups.keys())
@@ -201,7 +209,7 @@ def dedup_groups(groups, max_dist: int = 1, method: str = "directional", device:
         if where == "gpu":
             rep = _gpu_grouped(words, L, counts, offsets, max_dist, method)
         else:
-            rep = _host_grouped(words, L, counts, offsets, max_dist, METHODS[method])
+            rep = _host_grouped(words, L, counts, offsets, max_dist, GROUPED_METHODS[method])
         for (li, ki), r in zip(rows, rep):
             rep_of[li][ki] = rows[int(r)][1]
     out = {}

@@ -2,7 +2,7 @@
 """UMI clustering timings (DESIGN.md "UMI clustering"; the log is kept under profiles/cluster/).
 
 python tools/probe_cluster.py          ss_cluster_pairs alone and the whole batch.umi_cluster (HIP events),
-                                       both methods, against (a) ss_host_cluster_pairs on one core over
+                                       every method (cluster, directional, adjacency), against (a) ss_host_cluster_pairs on one core over
                                        the same pairs and (b) the ss_hamming_all_pairs_ex call that
                                        produced them: rounds, pairs/s, cluster step / (b)
 python tools/probe_cluster.py sweep    umi.dedup's two paths per length group (host: one ss_host_hamming
@@ -65,8 +65,8 @@ def case(n, L, k):
                                          tot.data_ptr(), 0, s), "all pairs")
     ap_med, ap_min = event_ms(all_pairs)
     order = torch.sort(counts, descending=True, stable=True).indices.to(torch.int32)
-    ws_bytes = int(L_.ss_cluster_ws_bytes(n, m))
-    ws = torch.empty(ws_bytes // 8 + 1, dtype=torch.int64, device=dev)
+    ws_sizes = {code: int(L_.ss_cluster_ws_bytes_method(n, m, code)) for code in B.CLUSTER_METHODS.values()}
+    ws = torch.empty(max(ws_sizes.values()) // 8 + 1, dtype=torch.int64, device=dev)
     rep = torch.empty(n, dtype=torch.int32, device=dev)
     sizes = torch.empty(n, dtype=torch.int32, device=dev)
     sums = torch.empty(n, dtype=torch.int64, device=dev)
@@ -76,6 +76,8 @@ def case(n, L, k):
     h_order = order.cpu().numpy().view(np.uint32)
     print(f"case n={n} L={L} k={k}: pairs={m}  all-pairs (b) median {ap_med:.3f} ms min {ap_min:.3f} ms", flush=True)
     for method, code in B.CLUSTER_METHODS.items():
+        ws_bytes = ws_sizes[code]
+
         def cluster():
             check(L_.ss_cluster_pairs(pairs.data_ptr(), m, n, counts.data_ptr(), order.data_ptr(), code, ws.data_ptr(),
                                       ws_bytes, rep.data_ptr(), sizes.data_ptr(), sums.data_ptr(), ncl.data_ptr(),
