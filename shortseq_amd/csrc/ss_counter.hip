@@ -2221,7 +2221,50 @@ __device__ __forceinline__ bool words_eq(const uint64_t* a, const uint64_t* b, u
     return eq;
 }
 
-// The same test for rows of a compile-time W1 words: each row read as the 16-B-aligned chunks
+// The probe of a key's slice in the global table, for passes that fold distinct keys into it
+// (ss_counter_merge_words and the drop-in engine's two class folds) in two phases: find, while the
+// table is stable (the key words of every resident key are complete), then claim and publish for the
+// keys not found.
+// slot_find: the slot whose key is fp and whose t.W key words equal kw, kEmpty when absent.  A null
+// kw: the key alone decides (a single-word table).
+__device__ __forceinline__ uint64_t slot_find(const Tbl& t, uint64_t fp, const uint64_t* kw) {
+    const uint64_t top = slot_top(t, fp), base = top & ~t.slice_mask;
+    uint64_t off = top & t.slice_mask;
+    for (uint64_t probe = 0; probe <= t.slice_mask; ++probe) {
+        const uint64_t k = t.slots[base + off].key;
+        if (k == kEmpty) break;
+        if (k == fp && (!kw || words_eq(t.keywords + (base + off) * t.W, kw, t.W))) return base + off;
+        off = (off + 1) & t.slice_mask;
+    }
+    return kEmpty;
+}
+
+// slot_claim: the first free slot of fp's slice, taken by a CAS on its key.  A slot another thread
+// claims meanwhile is never this thread's key (the keys of a pass are distinct), so claimed slots are
+// skipped without comparing words.  A slice without a free slot raises kOvfTable: kEmpty.
+__device__ __forceinline__ uint64_t slot_claim(const Tbl& t, uint64_t fp) {
+    const uint64_t top = slot_top(t, fp), base = top & ~t.slice_mask;
+    uint64_t off = top & t.slice_mask;
+    for (uint64_t probe = 0; probe <= t.slice_mask; ++probe) {
+        if (t.slots[base + off].key == kEmpty &&
+            atomicCAS(&t.slots[base + off].key, (unsigned long long)kEmpty, (unsigned long long)fp) == kEmpty)
+            return base + off;
+        off = (off + 1) & t.slice_mask;
+    }
+    atomicOr(t.overflow, kOvfTable);
+    return kEmpty;
+}
+
+// the claimed slot's key words, count and first index
+__device__ __forceinline__ void slot_publish(const Tbl& t, uint64_t at, const uint64_t* kw, uint32_t cnt,
+                                             uint32_t first) {
+    uint64_t* dst = t.keywords + at * t.W;
+    for (uint32_t q = 0; q < t.W; ++q) dst[q] = kw[q];
+    t.slots[at].ncount = ~cnt;
+    t.slots[at].first = first;
+}
+
+// words_eq for rows of a compile-time W1 words: each row read as the 16-B-aligned chunks
 // holding it, ceil((8 W1 + 8) / 16) dwordx4 gathers instead of W1 dwordx2 (the aggregate's row
 // gathers bound it on address processing, one cache line per lane per instruction).  An aligned
 // chunk never leaves the page of the row bytes it holds.  EVEN: W1 even and the rows' base 16-B
@@ -2473,27 +2516,13 @@ constexpr MwFpFn kMwFp[kMwAggFns] = {
 
 // Merge of already-counted multi-word entries (distinct keys: e.g. the extraction of another
 // table when a per-length table grows): phase 1 finds each entry's key among the slots that existed
-// before the merge (the table is stable during the pass, so the key words are complete); phase 2
-// gives the rest a fresh slot (a CAS on the fingerprint; a slot another entry claims is never this
-// entry's key, the entries being distinct, so claimed slots are skipped without comparing words)
-// and writes their key words, count and first index.  Found keys add count / min first.
+// before the merge (slot_find); phase 2 gives the rest a fresh slot (slot_claim) and writes their
+// key words, count and first index.  Found keys add count / min first.
 __global__ __launch_bounds__(256) void k_mw_merge_find(Tbl t, const uint64_t* __restrict__ words, uint64_t m,
                                                        uint64_t* __restrict__ found) {
     for (uint64_t e = (uint64_t)blockIdx.x * 256 + threadIdx.x; e < m; e += (uint64_t)gridDim.x * 256) {
         const uint64_t* kw = words + e * t.W;
-        const uint64_t fp = words_fp(kw, t.W);
-        const uint64_t top = slot_top(t, fp), base = top & ~t.slice_mask;
-        uint64_t off = top & t.slice_mask, at = kEmpty;
-        for (uint64_t probe = 0; probe <= t.slice_mask; ++probe) {
-            const uint64_t k = t.slots[base + off].key;
-            if (k == kEmpty) break;
-            if (k == fp && words_eq(t.keywords + (base + off) * t.W, kw, t.W)) {
-                at = base + off;
-                break;
-            }
-            off = (off + 1) & t.slice_mask;
-        }
-        found[e] = at;
+        found[e] = slot_find(t, words_fp(kw, t.W), kw);
     }
 }
 
@@ -2512,25 +2541,8 @@ __global__ __launch_bounds__(256) void k_mw_merge_claim(Tbl t, const uint64_t* _
         }
         uint64_t at = found[e];
         if (at == kEmpty) {
-            const uint64_t fp = words_fp(kw, t.W);
-            const uint64_t top = slot_top(t, fp), base = top & ~t.slice_mask;
-            uint64_t off = top & t.slice_mask;
-            for (uint64_t probe = 0; probe <= t.slice_mask; ++probe) {
-                if (t.slots[base + off].key == kEmpty &&
-                    atomicCAS(&t.slots[base + off].key, (unsigned long long)kEmpty, (unsigned long long)fp) == kEmpty) {
-                    at = base + off;
-                    break;
-                }
-                off = (off + 1) & t.slice_mask;
-            }
-            if (at == kEmpty) {
-                atomicOr(t.overflow, kOvfTable);
-                continue;
-            }
-            uint64_t* dst = t.keywords + at * t.W;
-            for (uint32_t q = 0; q < t.W; ++q) dst[q] = kw[q];
-            t.slots[at].ncount = ~c;
-            t.slots[at].first = (uint32_t)f;
+            if ((at = slot_claim(t, words_fp(kw, t.W))) == kEmpty) continue;
+            slot_publish(t, at, kw, c, (uint32_t)f);
             count_add_wide(t, at, 0u, c, chi);
             continue;
         }
@@ -2558,6 +2570,17 @@ __global__ __launch_bounds__(256) void k_prep(PrepWords w) {
 hipError_t launch_prep(const PrepWords& w, hipStream_t s) {
     hipLaunchKernelGGL(k_prep, dim3(1), dim3(256), 0, s, w);
     return hipGetLastError();
+}
+
+// Several tables' reset words in one dispatch (the drop-in engine resets up to six tables between
+// two kernels of a chunk; one launch each left ~5 us of command-processor gap between them)
+struct PrepMany {
+    unsigned long long* p[kPrepMany];
+    unsigned long long v[kPrepMany];
+    uint32_t n;
+};
+__global__ __launch_bounds__(64) void k_prep_many(PrepMany w) {
+    if (threadIdx.x < w.n) *w.p[threadIdx.x] = w.v[threadIdx.x];
 }
 
 Tbl tbl_of(const ss_counter* c) {
@@ -2608,6 +2631,21 @@ __global__ __launch_bounds__(256) void k_spill_wide(Tbl t) {
         const uint32_t cnt = ~sl.ncount, keep = sent ? 1u : 0u;
         if (cnt <= keep) continue;
         t.wide[s] += cnt - keep;
+        t.slots[s].ncount = ~keep;
+    }
+}
+
+// Counts moved out of the slots (the drop-in engine's spill, before a slot's u32 count could wrap):
+// acc[first] += count for every entry (first = the entry's row), the slot's count set to 0 -- the
+// sentinel slot (key ~0, present iff its count is nonzero) keeps 1 and spills count - 1.
+__global__ __launch_bounds__(256) void k_spill_counts(Tbl t, uint64_t* __restrict__ acc) {
+    for (uint64_t s = (uint64_t)blockIdx.x * 256 + threadIdx.x; s <= t.mask + 1; s += (uint64_t)gridDim.x * 256) {
+        const Slot sl = t.slots[s];
+        const bool sent = s > t.mask;
+        if (sent ? sl.ncount == 0xFFFFFFFFu : sl.key == kEmpty) continue;
+        const uint32_t cnt = ~sl.ncount, keep = sent ? 1u : 0u;
+        if (cnt <= keep || sl.first == kMaxIndex) continue;
+        acc[sl.first] += cnt - keep;
         t.slots[s].ncount = ~keep;
     }
 }
@@ -2861,10 +2899,6 @@ void launch_scan(const PartWs& w, uint32_t bins, uint32_t* start, hipStream_t s)
     hipLaunchKernelGGL(k_pc_offsets, dim3(bins), dim3(1024), 0, s, w, bins, (const uint32_t*)start);
 }
 
-}  // namespace
-
-extern "C" {
-
 // ------------------------------------------------------------------------------------------------
 // The drop-in engine's length classes counted by fingerprint (ss_classes_* in ss_internal.h).  The
 // classes' rows (W1 = W + 1 words: the read's words and its length) are counted by their 64-bit
@@ -2898,17 +2932,13 @@ __device__ __forceinline__ uint32_t cls_of(const ClsDesc& d, uint64_t g) {
     return c;
 }
 
-// the scratch slot holding key fp (kEmpty when absent)
-__device__ __forceinline__ uint64_t find_slot(const Tbl& t, uint64_t fp) {
-    const uint64_t top = slot_top(t, fp), base = top & ~t.slice_mask;
-    uint64_t off = top & t.slice_mask;
-    for (uint64_t probe = 0; probe <= t.slice_mask; ++probe) {
-        const uint64_t k = t.slots[base + off].key;
-        if (k == fp) return base + off;
-        if (k == kEmpty) return kEmpty;
-        off = (off + 1) & t.slice_mask;
-    }
-    return kEmpty;
+// the 64-B representative beside scratch slot s: eight u64, stored as four 16-B pieces
+__device__ __forceinline__ void rep_store(uint64_t* rep, uint64_t s, const uint64_t (&v)[8]) {
+    uint4* dst = (uint4*)(rep + s * 8);
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        dst[k] = make_uint4((uint32_t)v[2 * k], (uint32_t)(v[2 * k] >> 32), (uint32_t)v[2 * k + 1],
+                            (uint32_t)(v[2 * k + 1] >> 32));
 }
 
 __global__ __launch_bounds__(256) void k_cls_verify(Tbl f, ClsDesc d, const uint64_t* __restrict__ fps,
@@ -2916,7 +2946,7 @@ __global__ __launch_bounds__(256) void k_cls_verify(Tbl f, ClsDesc d, const uint
     const uint64_t n = d.row0[d.ncls];
     for (uint64_t g = (uint64_t)blockIdx.x * 256 + threadIdx.x; g < n; g += (uint64_t)gridDim.x * 256) {
         const uint32_t c = cls_of(d, g);
-        const uint64_t sl = find_slot(f, fps[g]);
+        const uint64_t sl = slot_find(f, fps[g], nullptr);     // (the scratch is a single-word table)
         bool bad = sl == kEmpty;
         if (!bad) {
             const uint64_t rep = f.slots[sl].first;
@@ -2951,10 +2981,7 @@ __global__ __launch_bounds__(256) void k_cls_reps(Tbl f, ClsDesc d, uint64_t* __
             for (uint32_t j = 0; j < d.W1[c]; ++j) v[1 + j] = kw[j];
             v[7] = c;
         }
-        uint4* dst = (uint4*)(rep + s * 8);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) dst[k] = make_uint4((uint32_t)v[2 * k], (uint32_t)(v[2 * k] >> 32), (uint32_t)v[2 * k + 1],
-                                                       (uint32_t)(v[2 * k + 1] >> 32));
+        rep_store(rep, s, v);
     }
 }
 
@@ -3039,22 +3066,7 @@ __global__ __launch_bounds__(256) void k_cls_fold_find(Tbl f, ClsDesc d, const u
         uint64_t fp, first;
         uint32_t cnt, c;
         const uint64_t* kw;
-        uint64_t at = kEmpty;
-        if (fold_entry(f, d, s, fp, cnt, c, kw, first)) {
-            const Tbl& t = d.tbl[c];
-            const uint64_t top = slot_top(t, fp), base = top & ~t.slice_mask;
-            uint64_t off = top & t.slice_mask;
-            for (uint64_t probe = 0; probe <= t.slice_mask; ++probe) {
-                const uint64_t k = t.slots[base + off].key;
-                if (k == kEmpty) break;
-                if (k == fp && words_eq(t.keywords + (base + off) * t.W, kw, t.W)) {
-                    at = base + off;
-                    break;
-                }
-                off = (off + 1) & t.slice_mask;
-            }
-        }
-        found[s] = at;
+        found[s] = fold_entry(f, d, s, fp, cnt, c, kw, first) ? slot_find(d.tbl[c], fp, kw) : kEmpty;
     }
 }
 
@@ -3073,24 +3085,7 @@ __global__ __launch_bounds__(256) void k_cls_fold_claim(Tbl f, ClsDesc d, const 
         }
         uint64_t at = found[s];
         if (at == kEmpty) {
-            const uint64_t top = slot_top(t, fp), base = top & ~t.slice_mask;
-            uint64_t off = top & t.slice_mask;
-            for (uint64_t probe = 0; probe <= t.slice_mask; ++probe) {
-                if (t.slots[base + off].key == kEmpty &&
-                    atomicCAS(&t.slots[base + off].key, (unsigned long long)kEmpty, (unsigned long long)fp) == kEmpty) {
-                    at = base + off;
-                    break;
-                }
-                off = (off + 1) & t.slice_mask;
-            }
-            if (at == kEmpty) {
-                atomicOr(t.overflow, kOvfTable);
-                continue;
-            }
-            uint64_t* dst = t.keywords + at * t.W;
-            for (uint32_t q = 0; q < t.W; ++q) dst[q] = kw[q];
-            t.slots[at].ncount = ~cnt;
-            t.slots[at].first = (uint32_t)first;
+            if ((at = slot_claim(t, fp)) != kEmpty) slot_publish(t, at, kw, cnt, (uint32_t)first);
             continue;
         }
         atomicAdd(&t.slots[at].ncount, 0u - cnt);
@@ -3149,11 +3144,7 @@ __global__ __launch_bounds__(256) void k_flat_reps(Tbl f, const uint64_t* __rest
                 w[j] = (used && j < S) ? v[u][j] : 0ull;
                 if (w[j]) w[7] = j;
             }
-            uint4* dst = (uint4*)(rep + s * 8);
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                dst[k] = make_uint4((uint32_t)w[2 * k], (uint32_t)(w[2 * k] >> 32), (uint32_t)w[2 * k + 1],
-                                    (uint32_t)(w[2 * k + 1] >> 32));
+            rep_store(rep, s, w);
         }
     }
 }
@@ -3239,21 +3230,28 @@ __global__ __launch_bounds__(256) void k_flat_verify(Tbl f, const uint64_t* __re
     if (__ballot(bad) && bad) atomicOr(flag, 1u);
 }
 
-// scratch slot s -> (fp, count, first read, class W, the rep's words); false for a free slot, the
-// zero row's entry, or a class without a table
+// What of the scratch is an entry the fold takes, on loaded values: slot s of the table (sl: its
+// key, ~count, first read) holds a key, and its class W (rep word 7; 0 for the zero row's entry) is
+// one of 2 .. S - 1 with a table.
+__device__ __forceinline__ bool flat_decode(const Tbl& f, const FlatDesc& d, uint64_t s, const uint4& sl, uint32_t w7,
+                                            uint32_t& cnt, uint32_t& W, uint64_t& first) {
+    if (s > f.mask || (sl.x == 0xFFFFFFFFu && sl.y == 0xFFFFFFFFu)) return false;   // (kEmpty key)
+    W = w7;
+    if (W < 2 || W + 1 > d.S || !d.tbl[W].slots) return false;
+    cnt = ~sl.z;
+    first = sl.w;
+    return true;
+}
+
+// scratch slot s <= f.mask -> (fp, count, first read, class W, the rep's words), or false: no entry.
+// The slot, then (of a used slot) its class word.
 __device__ __forceinline__ bool flat_entry(const Tbl& f, const FlatDesc& d, const uint64_t* rep, uint64_t s,
                                            uint64_t& fp, uint32_t& cnt, uint32_t& W, const uint64_t*& kw,
                                            uint64_t& first) {
-    if (s > f.mask) return false;
-    const Slot sl = f.slots[s];
-    if (sl.key == kEmpty) return false;
-    W = (uint32_t)rep[s * 8 + 7];
-    if (W < 2 || W + 1 > d.S || !d.tbl[W].slots) return false;
-    fp = sl.key;
-    cnt = ~sl.ncount;
-    first = sl.first;
+    const uint4 sl = *(const uint4*)&f.slots[s];
+    fp = (uint64_t)sl.y << 32 | sl.x;
     kw = rep + s * 8;
-    return true;
+    return flat_decode(f, d, s, sl, fp != kEmpty ? (uint32_t)kw[7] : 0u, cnt, W, first);
 }
 
 // find: the class table slot of each entry's key (kEmpty: a new key), and per block the new keys of
@@ -3263,7 +3261,6 @@ __device__ __forceinline__ bool flat_entry(const Tbl& f, const FlatDesc& d, cons
 // 3.1 ms on the f2 batch)
 // EXTRACT (the class tables are known to be empty, ss_classes_flat_extract): every entry is new, no
 // probe; found is not written
-extern "C++" {      // (a template inside this file's extern "C" section)
 // The extract's entry loads, all issued together: the slot and its whole 64-B representative (the
 // words, the key, the class) do not depend on each other, so a grid-stride step waits one round
 // trip instead of three (slot -> class -> words, as flat_entry does); kFlatXU slots per step are in
@@ -3279,16 +3276,6 @@ __device__ __forceinline__ void flat_load(const Tbl& f, const uint64_t* rep, uin
     const uint4* rp = (const uint4*)(rep + sc * 8);
 #pragma unroll
     for (int k = 0; k < 4; ++k) e.r[k] = rp[k];
-}
-// flat_entry's rule on loaded values: the class W (rep word 7) and the slot's count and first read
-__device__ __forceinline__ bool flat_decode(const Tbl& f, const FlatDesc& d, uint64_t s, const FlatLoad& e,
-                                            uint32_t& cnt, uint32_t& W, uint64_t& first) {
-    if (s > f.mask || (e.sl.x == 0xFFFFFFFFu && e.sl.y == 0xFFFFFFFFu)) return false;   // (kEmpty key)
-    W = e.r[3].z;
-    if (W < 2 || W + 1 > d.S || !d.tbl[W].slots) return false;
-    cnt = ~e.sl.z;
-    first = e.sl.w;
-    return true;
 }
 
 template <bool EXTRACT>
@@ -3314,18 +3301,7 @@ __global__ __launch_bounds__(256) void k_flat_fold_find(Tbl f, FlatDesc d, const
             uint32_t cnt, W;
             const uint64_t* kw;
             if (flat_entry(f, d, rep, s, fp, cnt, W, kw, first)) {
-                const Tbl& t = d.tbl[W];
-                const uint64_t top = slot_top(t, fp), base = top & ~t.slice_mask;
-                uint64_t off = top & t.slice_mask;
-                for (uint64_t probe = 0; probe <= t.slice_mask; ++probe) {
-                    const uint64_t k = t.slots[base + off].key;
-                    if (k == kEmpty) break;
-                    if (k == fp && words_eq(t.keywords + (base + off) * t.W, kw, t.W)) {
-                        at = base + off;
-                        break;
-                    }
-                    off = (off + 1) & t.slice_mask;
-                }
+                at = slot_find(d.tbl[W], fp, kw);
                 if (at == kEmpty) atomicAdd(&lc[W], 1u);
             }
             found[s] = at;
@@ -3334,7 +3310,6 @@ __global__ __launch_bounds__(256) void k_flat_fold_find(Tbl f, FlatDesc d, const
     __syncthreads();
     if (threadIdx.x < kRepW1) blkcnt[(uint64_t)blockIdx.x * kRepW1 + threadIdx.x] = lc[threadIdx.x];
 }
-}  // extern "C++"
 
 // one block: blkcnt -> each block's first row per class (exclusive scan over the blocks, in place)
 struct FlatTotals {
@@ -3403,24 +3378,8 @@ __global__ __launch_bounds__(256) void k_flat_fold_claim(Tbl f, FlatDesc d, cons
             atomicOr(t.overflow, kOvfIndex);
             trow = kMaxIndex;
         }
-        const uint64_t top = slot_top(t, fp), base = top & ~t.slice_mask;
-        uint64_t off = top & t.slice_mask, at = kEmpty;
-        for (uint64_t probe = 0; probe <= t.slice_mask; ++probe) {
-            if (t.slots[base + off].key == kEmpty &&
-                atomicCAS(&t.slots[base + off].key, (unsigned long long)kEmpty, (unsigned long long)fp) == kEmpty) {
-                at = base + off;
-                break;
-            }
-            off = (off + 1) & t.slice_mask;
-        }
-        if (at == kEmpty) {
-            atomicOr(t.overflow, kOvfTable);
-            continue;
-        }
-        uint64_t* dst = t.keywords + at * t.W;
-        for (uint32_t q = 0; q < t.W; ++q) dst[q] = kw[q];
-        t.slots[at].ncount = ~cnt;
-        t.slots[at].first = (uint32_t)trow;
+        const uint64_t at = slot_claim(t, fp);
+        if (at != kEmpty) slot_publish(t, at, kw, cnt, (uint32_t)trow);
     }
 }
 
@@ -3451,7 +3410,7 @@ __global__ __launch_bounds__(256) void k_flat_extract_claim(Tbl f, FlatDesc d, F
         for (int u = 0; u < kFlatXU; ++u) {
             uint64_t first;
             uint32_t cnt, W;
-            if (!flat_decode(f, d, s0 + u * stride, e[u], cnt, W, first)) continue;
+            if (!flat_decode(f, d, s0 + u * stride, e[u].sl, e[u].r[3].z, cnt, W, first)) continue;
             const uint32_t row = atomicAdd(&lc[W], 1u);     // LDS: this block's next row of class W
             if (row >= o.cap[W]) {
                 atomicOr(o.ovf[W], (unsigned long long)kOvfTable);
@@ -3469,6 +3428,10 @@ __global__ __launch_bounds__(256) void k_flat_extract_claim(Tbl f, FlatDesc d, F
         }
     }
 }
+
+}  // namespace
+
+extern "C" {
 
 int ss_counter_create(uint64_t capacity, ss_counter** out) {
     if (!out) return ss_fail(SS_EARG, "null out");
@@ -3598,17 +3561,6 @@ int ss_counter_reset(ss_counter* c, void* stream) {
     const int rc = ss_counter_reset_host(c, w.p, w.v);
     if (rc) return rc;
     return ss_check(launch_prep(w, (hipStream_t)stream), "ss_counter_reset");
-}
-
-// Several tables' reset words in one dispatch (the drop-in engine resets up to six tables between
-// two kernels of a chunk; one launch each left ~5 us of command-processor gap between them)
-struct PrepMany {
-    unsigned long long* p[kPrepMany];
-    unsigned long long v[kPrepMany];
-    uint32_t n;
-};
-__global__ __launch_bounds__(64) void k_prep_many(PrepMany w) {
-    if (threadIdx.x < w.n) *w.p[threadIdx.x] = w.v[threadIdx.x];
 }
 
 int ss_prep_words(unsigned long long* const* p, const unsigned long long* v, uint32_t n, void* stream) {
@@ -4157,21 +4109,6 @@ int ss_counter_extract_words(ss_counter* c, uint32_t n_parts, uint64_t* d_fps, u
 
 }  // extern "C"
 
-// Counts moved out of the slots (the drop-in engine's spill, before a slot's u32 count could wrap):
-// acc[first] += count for every entry (first = the entry's row), the slot's count set to 0 -- the
-// sentinel slot (key ~0, present iff its count is nonzero) keeps 1 and spills count - 1.
-__global__ __launch_bounds__(256) void k_spill_counts(Tbl t, uint64_t* __restrict__ acc) {
-    for (uint64_t s = (uint64_t)blockIdx.x * 256 + threadIdx.x; s <= t.mask + 1; s += (uint64_t)gridDim.x * 256) {
-        const Slot sl = t.slots[s];
-        const bool sent = s > t.mask;
-        if (sent ? sl.ncount == 0xFFFFFFFFu : sl.key == kEmpty) continue;
-        const uint32_t cnt = ~sl.ncount, keep = sent ? 1u : 0u;
-        if (cnt <= keep || sl.first == kMaxIndex) continue;
-        acc[sl.first] += cnt - keep;
-        t.slots[s].ncount = ~keep;
-    }
-}
-
 int ss_counter_spill_counts(ss_counter* c, uint64_t* d_acc, void* stream) {
     if (!c || !d_acc) return ss_fail(SS_EARG, "null argument");
     hipStream_t s = (hipStream_t)stream;
@@ -4189,14 +4126,23 @@ int ss_counter_set_spill_limit(ss_counter* c, uint64_t reads) {
     return SS_OK;
 }
 
-// the scratch of the read-order path: rep[(cap + 1) * 8], found[cap + 1], then the per-block class
-// counts / first rows (fpt's aux buffer: it outlives the call, a deferred fold or extract reads it)
-static int flat_scratch(ss_counter* fpt, unsigned grid, uint64_t** rep, uint64_t** found, uint32_t** blk) {
-    const uint64_t fwords = fpt->cap + 1 + ((uint64_t)grid * kRepW1 + 1) / 2;
-    int rc = aux_scratch(fpt, ((fpt->cap + 1) * 8 + fwords) * sizeof(uint64_t), (void**)rep);
+// what the read-order path's calls share: the scratch table, the grid of its per-slot kernels, and
+// rep[(cap + 1) * 8], found[cap + 1], then the per-block class counts / first rows (fpt's aux
+// buffer: it outlives the call, a deferred fold or extract reads it)
+struct FlatWs {
+    Tbl f;
+    unsigned grid;
+    uint64_t *rep, *found;
+    uint32_t* blk;
+};
+static int flat_scratch(ss_counter* fpt, FlatWs& w) {
+    w.f = tbl_of(fpt);
+    w.grid = grid_for(fpt->cap, 256, 256 * 16);
+    const uint64_t fwords = fpt->cap + 1 + ((uint64_t)w.grid * kRepW1 + 1) / 2;
+    int rc = aux_scratch(fpt, ((fpt->cap + 1) * 8 + fwords) * sizeof(uint64_t), (void**)&w.rep);
     if (rc) return rc;
-    *found = *rep + (fpt->cap + 1) * 8;
-    *blk = (uint32_t*)(*found + fpt->cap + 1);
+    w.found = w.rep + (fpt->cap + 1) * 8;
+    w.blk = (uint32_t*)(w.found + fpt->cap + 1);
     return SS_OK;
 }
 
@@ -4208,15 +4154,11 @@ static int flat_desc(const ss_flat_class* cls, uint32_t S, uint64_t base, hipStr
         ss_counter* t = cls[W].table;
         if (!t) continue;
         if (t->L != kWordKeys || t->W != W + 1) return ss_fail(SS_EARG, "class table: set_words(W + 1) first");
-        if (!flush) {
-            d.tbl[W] = tbl_of(t);
-            d.row0[W] = cls[W].base;
-            d.rmap[W] = cls[W].rmap;
-            continue;
+        if (flush) {
+            int rc = flush_reset(t, s);
+            if (rc) return rc;
+            t->occ_src = 0;
         }
-        int rc = flush_reset(t, s);
-        if (rc) return rc;
-        t->occ_src = 0;
         d.tbl[W] = tbl_of(t);
         d.row0[W] = cls[W].base;
         d.rmap[W] = cls[W].rmap;
@@ -4232,17 +4174,14 @@ int ss_classes_flat_verify(ss_counter* fpt, const uint64_t* d_rows, uint32_t S, 
     hipStream_t s = (hipStream_t)stream;
     int rc = flush_reset(fpt, s);
     if (rc) return rc;
-    const Tbl f = tbl_of(fpt);
-    const unsigned grid = grid_for(fpt->cap, 256, 256 * 16);
-    uint64_t *rep = nullptr, *found = nullptr;
-    uint32_t* blk = nullptr;
-    if ((rc = flat_scratch(fpt, grid, &rep, &found, &blk))) return rc;
-    hipLaunchKernelGGL(k_flat_reps, dim3(grid), dim3(256), 0, s, f, d_rows, S, rep);
+    FlatWs w;
+    if ((rc = flat_scratch(fpt, w))) return rc;
+    hipLaunchKernelGGL(k_flat_reps, dim3(w.grid), dim3(256), 0, s, w.f, d_rows, S, w.rep);
     if (ev_reps && (rc = ss_check(hipEventRecord((hipEvent_t)ev_reps, s), "class reps event"))) return rc;
     // one short block per 64 kFlatQK rows (no persistent grid): a kernel queued on another stream
     // beside the verify (the speculative finish) gets CU slots as the verify's blocks retire
-    hipLaunchKernelGGL(k_flat_verify, dim3(grid_for(n, 64 * kFlatQK, 0)), dim3(256), 0, s, f, d_rows, S, n, d_fps,
-                       (const uint64_t*)rep, d_flag);
+    hipLaunchKernelGGL(k_flat_verify, dim3(grid_for(n, 64 * kFlatQK, 0)), dim3(256), 0, s, w.f, d_rows, S, n, d_fps,
+                       (const uint64_t*)w.rep, d_flag);
     return ss_check(hipGetLastError(), "class verify (read-order rows)");
 }
 
@@ -4253,15 +4192,13 @@ int ss_classes_flat_fold(ss_counter* fpt, uint32_t S, const ss_flat_class* cls, 
     FlatDesc d;
     int rc = flat_desc(cls, S, base, s, d);
     if (rc) return rc;
-    const Tbl f = tbl_of(fpt);
-    const unsigned grid = grid_for(fpt->cap, 256, 256 * 16);
-    uint64_t *rep = nullptr, *found = nullptr;
-    uint32_t* blk = nullptr;
-    if ((rc = flat_scratch(fpt, grid, &rep, &found, &blk))) return rc;
-    hipLaunchKernelGGL(k_flat_fold_find<false>, dim3(grid), dim3(256), 0, s, f, d, (const uint64_t*)rep, d_flag, found, blk);
-    hipLaunchKernelGGL(k_flat_fold_scan, dim3(1), dim3(256), 0, s, blk, grid, FlatTotals{});
-    hipLaunchKernelGGL(k_flat_fold_claim, dim3(grid), dim3(256), 0, s, f, d, (const uint64_t*)rep, d_flag,
-                       (const uint64_t*)found, (const uint32_t*)blk);
+    FlatWs w;
+    if ((rc = flat_scratch(fpt, w))) return rc;
+    hipLaunchKernelGGL(k_flat_fold_find<false>, dim3(w.grid), dim3(256), 0, s, w.f, d, (const uint64_t*)w.rep, d_flag,
+                       w.found, w.blk);
+    hipLaunchKernelGGL(k_flat_fold_scan, dim3(1), dim3(256), 0, s, w.blk, w.grid, FlatTotals{});
+    hipLaunchKernelGGL(k_flat_fold_claim, dim3(w.grid), dim3(256), 0, s, w.f, d, (const uint64_t*)w.rep, d_flag,
+                       (const uint64_t*)w.found, (const uint32_t*)w.blk);
     return ss_check(hipGetLastError(), "class fold (read-order rows)");
 }
 
@@ -4287,15 +4224,13 @@ int ss_classes_flat_extract(ss_counter* fpt, uint32_t S, const ss_flat_class* cl
         o.cap[W] = out[W].cap;
         tot.p[W] = out[W].total;
     }
-    const Tbl f = tbl_of(fpt);
-    const unsigned grid = grid_for(fpt->cap, 256, 256 * 16);
-    uint64_t *rep = nullptr, *found = nullptr;
-    uint32_t* blk = nullptr;
-    if ((rc = flat_scratch(fpt, grid, &rep, &found, &blk))) return rc;
-    hipLaunchKernelGGL(k_flat_fold_find<true>, dim3(grid), dim3(256), 0, s, f, d, (const uint64_t*)rep, d_zero, found, blk);
-    hipLaunchKernelGGL(k_flat_fold_scan, dim3(1), dim3(256), 0, s, blk, grid, tot);
-    hipLaunchKernelGGL(k_flat_extract_claim, dim3(grid), dim3(256), 0, s, f, d, o, (const uint64_t*)rep,
-                       (const uint32_t*)blk);
+    FlatWs w;
+    if ((rc = flat_scratch(fpt, w))) return rc;
+    hipLaunchKernelGGL(k_flat_fold_find<true>, dim3(w.grid), dim3(256), 0, s, w.f, d, (const uint64_t*)w.rep, d_zero,
+                       w.found, w.blk);
+    hipLaunchKernelGGL(k_flat_fold_scan, dim3(1), dim3(256), 0, s, w.blk, w.grid, tot);
+    hipLaunchKernelGGL(k_flat_extract_claim, dim3(w.grid), dim3(256), 0, s, w.f, d, o, (const uint64_t*)w.rep,
+                       (const uint32_t*)w.blk);
     return ss_check(hipGetLastError(), "class extract (read-order rows)");
 }
 

@@ -431,3 +431,79 @@ def test_counter_reset_drops_u64_counts(gpu, oracle, partitioned):
         _assert_pack_clean(t, d2)
     finally:
         t.close()
+
+
+# ------------------------------------------------------------------------------------------------
+# E. merge_words: the two exits of its claim phase (slice full, first index past the field)
+# ------------------------------------------------------------------------------------------------
+OVF_TABLE = 1                   # overflow word: a key found no free slot in its slice
+OVF_INDEX = 8                   # overflow word: a first index was clamped to 0xFFFFFFFE
+
+
+def _merge_rows(t, gpu, rows):
+    """rows [(words tuple, count, first)] -> one merge_words call."""
+    import torch
+    W = len(rows[0][0])
+    ww = np.array([w for (w, _c, _f) in rows], dtype=np.uint64).view(np.int64).reshape(len(rows), W)
+    t.merge_words(torch.from_numpy(ww).to(gpu),
+                  torch.tensor([c for (_w, c, _f) in rows], dtype=torch.int64, device=gpu),
+                  torch.tensor([f for (_w, _c, f) in rows], dtype=torch.int64, device=gpu))
+
+
+def _words_dict(t):
+    """extract_words(1) -> {words tuple: (count, first)}; no look at the overflow word."""
+    _fps, _lens, words, counts, first, parts = t.extract_words(1)
+    m = int(parts.sum().item())
+    w = words[:m].cpu().numpy().view(np.uint64).tolist()
+    d = {tuple(r): (int(c), int(f)) for r, c, f in zip(w, counts[:m].tolist(), first[:m].tolist())}
+    assert len(d) == m, "a key extracted twice"
+    return d
+
+
+@pytest.mark.parametrize("W", [2, 3, 7])
+def test_counter_merge_words_slice_full(gpu, W):
+    """96 distinct rows merged into a 64-slot table (one region, one slice): the overflow word is the
+    table-full bit alone, exactly 64 of the rows are resident, each with its own count and first; the
+    same 96 rows again double the 64 counts, keep the firsts, admit no other key, keep the bit."""
+    import shortseq_amd.batch as B
+    from shortseq_amd._native import check, lib
+    rng = np.random.default_rng(200 + W)
+    raw = rng.integers(0, 1 << 64, size=(96, W), dtype=np.uint64)
+    rows = [(tuple(int(x) for x in r), 1 + i, i) for i, r in enumerate(raw)]
+    src = {w: (c, f) for (w, c, f) in rows}
+    assert len(src) == 96
+    t = B.GpuCounter(64, device=gpu)
+    try:
+        assert t.capacity == 64
+        check(lib().ss_counter_set_words(t._h, W), "ss_counter_set_words")
+        _merge_rows(t, gpu, rows)
+        assert int(t.overflow_word().item()) == OVF_TABLE
+        got = _words_dict(t)
+        assert len(got) == 64
+        assert all(src[w] == v for w, v in got.items())
+        _merge_rows(t, gpu, rows)
+        got2 = _words_dict(t)
+        assert got2 == {w: (2 * c, f) for w, (c, f) in got.items()}
+        assert int(t.overflow_word().item()) == OVF_TABLE
+    finally:
+        t.close()
+
+
+def test_counter_merge_words_first_past_field(gpu):
+    """Firsts of 2^32 + 9 merged onto a resident key and with a new key: the overflow word is the
+    index bit alone, the resident key keeps its first, the new key gets 0xFFFFFFFE; a resident key
+    merged with a smaller first takes it; counts exact."""
+    import torch
+    import shortseq_amd.batch as B
+    W = 2
+    raw = np.random.default_rng(210).integers(0, 1 << 64, size=(3, W), dtype=np.uint64)
+    ka, kb, kc = (tuple(int(x) for x in r) for r in raw)
+    t = B.GpuCounter(1 << 12, device=gpu)
+    try:
+        t.insert_words(torch.from_numpy(raw[:2].view(np.int64).copy()).to(gpu), base_index=5)
+        assert _words_dict(t) == {ka: (1, 5), kb: (1, 6)}
+        _merge_rows(t, gpu, [(ka, 10, (1 << 32) + 9), (kb, 20, 2), (kc, 30, (1 << 32) + 9)])
+        assert int(t.overflow_word().item()) == OVF_INDEX
+        assert _words_dict(t) == {ka: (11, 5), kb: (21, 2), kc: (30, 0xFFFFFFFE)}
+    finally:
+        t.close()

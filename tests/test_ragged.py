@@ -127,6 +127,33 @@ def test_device_ingest_undersized_class_table_recounts(gpu, oracle):
     assert gl.tolist() == el.tolist() and gc.tolist() == ec.tolist() and np.array_equal(gw, ew)
 
 
+def test_device_ingest_undersized_class_table_recounts_class_ordered(gpu, oracle):
+    """The same with reads of 1-150 nt: short reads sit beside the classes, so the chunk takes the
+    class-ordered rows and the undersized class tables run full in k_cls_fold_claim."""
+    import shortseq_amd.batch as B
+    from shortseq_amd._native import NativeError
+    seed, ps, U, n, lo, hi = 53, 54, 1 << 17, 400_000, 1, 150
+    blob, offs, lens = B.synth_ragged_pool_reads(n, seed, ps, U, lo, hi, device=gpu)
+    eng = B.DeviceIngest(gpu, _sizing=2)
+    try:
+        eng.count(blob, offs, lens)
+        assert eng.retried
+        gl, gc, gw = eng.results()
+        eng.reset()
+        eng.count(blob, offs[:1000], lens[:1000])           # small: fits even undersized
+        with pytest.raises(NativeError, match="ran full"):
+            eng.count(blob, offs, lens)
+        with pytest.raises(NativeError, match="reset and count again"):   # the counts are void now
+            eng.results()
+        eng.reset()
+        eng.count(blob, offs[:1000], lens[:1000])
+        assert int(eng.results()[1].sum()) == 1000
+    finally:
+        eng.close()
+    el, ec, ew = oracle.ragged_pool_rows(seed, ps, U, n, lo, hi)
+    assert gl.tolist() == el.tolist() and gc.tolist() == ec.tolist() and np.array_equal(gw, ew)
+
+
 def test_device_ingest_class_lengths_apart(gpu, oracle):
     """One length class (33..64 nt) holds reads that pack to the same words at different lengths
     (trailing 'A' = code 0): the class key's length word keeps them apart, as the reference's
