@@ -500,6 +500,51 @@ int ss_fastq_index_onepass(const uint8_t* d_buf, uint64_t nbytes, uint64_t line0
 int ss_gather_rows(const uint8_t* d_src, uint64_t src_bytes, const uint64_t* d_offsets, const uint64_t* d_sel,
                    uint64_t m, uint32_t L, uint8_t* d_dst, uint64_t dst_stride, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * 3' adapter trim of a ragged batch (small-RNA and amplicon libraries: almost every read runs through
+ * the insert into the 3' adapter; new in this ABI version, replaces no reference interface).  No read
+ * is moved: d_out_lens[i] is read i's length lowered to the adapter's position, and (d_offsets,
+ * d_out_lens) is again the ragged layout of ss_encode_var, ss_gather_rows and ss_ingest_add_device.
+ * The rule, for a read r[0..L), an adapter a[0..A) with 1 <= A <= 64, min_overlap >= 1, err_div >= 0:
+ *   for a position p in 0 .. L-1:  ov(p) = min(A, L - p);
+ *     mm(p) = the number of k < ov(p) with a[k] != 'N' and r[p + k] != a[k];
+ *     p matches iff ov(p) >= min_overlap and mm(p) <= (err_div ? ov(p) / err_div : 0)  (integer division);
+ *   the trimmed length is the LEAST matching p, or L when none matches.
+ * Comparison is bytewise and case-sensitive: an 'N', a lower-case letter or any other byte in the READ
+ * is an ordinary mismatch; only an 'N' in the adapter is a wildcard.  The match is leftmost, not
+ * best-scoring, and has no indels; err_div = 10 is the floor(0.1 * overlap) mismatch budget.  With
+ * err_div = 1 every position with enough overlap matches (a read of L >= min_overlap trims to 0), and
+ * a short overlap matches by chance (3 bytes: one time in 64), as in every adapter trimmer.
+ * Reads with d_lens[i] > SS_MAX_NT (0xFFFFFFFF, the strlen - 1 underflow of ss_fastq_index, included)
+ * are left as they are and none of their bytes is read: they stay the too-long error.  Length 0 stays 0.
+ * The device entry points keep the plain contract (asynchronous on `stream`, no allocation, no
+ * synchronisation, capturable); the adapter travels in the kernel arguments (h_adapter is read before
+ * the call returns).  d_out_lens may be d_lens itself.  d_stats (nullable): u64[2] = {reads shortened,
+ * bytes removed}, zeroed by the entry point.  n < 2^32.  The blob is read in whole 16-B aligned chunks
+ * around each read, as by ss_encode_var: it must be readable to the end of its last 16-B chunk (every
+ * device allocation is); offsets and lengths are trusted to lie inside it.
+ * reads_per_launch (_ex; a test hook): reads per kernel launch, 0 = the library's 2^28 (larger values
+ * are clamped to it); the results do not depend on it.
+ * Kernel (k_trim_adapter3): a group of 4 lanes per read stages the read's chunks in LDS and shares its
+ * positions in rounds; one position is a SWAR pass over 8 bytes at a time (xor the adapter word, wildcard and
+ * overlap masks, nonzero-byte mask, popcount), left as soon as the budget is passed; the group's
+ * least match from the wave ballot ("3' adapter trim").
+ * SS_EARG (nothing is written): a NULL required pointer with n > 0 (d_blob, d_offsets, d_lens,
+ * h_adapter, d_out_lens), A == 0 or A > 64, min_overlap == 0, n >= 2^32.
+ * ss_host_trim_adapter3: the same function in plain C++ on host arrays (csrc/host_trim.h per read); it
+ * also validates h_offsets[i] + h_lens[i] <= nbytes for every read with h_lens[i] <= SS_MAX_NT
+ * (SS_EARG, checked before anything is written).
+ * ---------------------------------------------------------------------------------------------- */
+int ss_trim_adapter3(const uint8_t* d_blob, uint64_t nbytes, const uint64_t* d_offsets, const uint32_t* d_lens,
+                     uint64_t n, const uint8_t* h_adapter, uint32_t A, uint32_t min_overlap, uint32_t err_div,
+                     uint32_t* d_out_lens, uint64_t* d_stats, void* stream);
+int ss_trim_adapter3_ex(const uint8_t* d_blob, uint64_t nbytes, const uint64_t* d_offsets, const uint32_t* d_lens,
+                        uint64_t n, const uint8_t* h_adapter, uint32_t A, uint32_t min_overlap, uint32_t err_div,
+                        uint32_t* d_out_lens, uint64_t* d_stats, uint64_t reads_per_launch, void* stream);
+int ss_host_trim_adapter3(const uint8_t* h_blob, uint64_t nbytes, const uint64_t* h_offsets, const uint32_t* h_lens,
+                          uint64_t n, const uint8_t* h_adapter, uint32_t A, uint32_t min_overlap, uint32_t err_div,
+                          uint32_t* h_out_lens, uint64_t* h_stats);
+
 /* Multi-GPU counter with region-range ownership: part p of n owns the table regions
  * [ceil(p R / n), ceil((p + 1) R / n)) (R = capacity / slice slots, ss_counter_geometry); the sentinel
  * key ~0 belongs to the owner of its hash region.  Every rank counts its own reads into its own
@@ -578,6 +623,17 @@ int ss_ingest_create(int device, ss_ingest** h_out);
 int ss_ingest_destroy(ss_ingest* g);
 int ss_ingest_reset(ss_ingest* g);
 int ss_ingest_set_exact(ss_ingest* g, int exact);
+/* 3' adapter of the engine (the rule of ss_trim_adapter3; new in this ABI version): every later
+ * ss_ingest_add_blob, _add_device, _add_fastq and _add_fastq_range trims each chunk's lengths once, on the
+ * engine's stream, before anything else sees them (a FASTQ chunk in place right after its index, as
+ * part of the index stage; a staged list never as a dense chunk; a caller's device lengths into the
+ * engine's own array: the caller's are never written).  Everything after that is unchanged: the first
+ * rejected read is judged on its kept prefix only (a bad byte in the removed tail is no error),
+ * ss_ingest_error returns the trimmed bytes, a read trimmed to 0 counts as the empty read, and a line
+ * of more than 1024 bytes is still the too-long error.  A == 0 clears the setting; it is sticky across
+ * ss_ingest_reset, like ss_ingest_set_exact.  SS_EARG: A > 64, or A > 0 with a NULL adapter or
+ * min_overlap == 0.  With no adapter set no kernel is queued and no buffer is touched. */
+int ss_ingest_set_adapter(ss_ingest* g, const uint8_t* h_adapter, uint32_t A, uint32_t min_overlap, uint32_t err_div);
 /* Global read indices of one engine are u64 (a call counts any number of reads); a length's or class's
  * table indexes its rows with a u32 first index, so a group about to pass 2^32 - 1 rows is re-keyed
  * (its distinct keys become its first rows).  Test hook: lower that bound to `rows` (>= 1024) so the

@@ -30,7 +30,8 @@ _NO_BAD = -1  # UINT64_MAX viewed as int64
 __all__ = ["words_for", "wpr_for", "encode", "encode_var", "decode", "decode_var", "hamming_ref",
            "hamming_pair", "encode_hamming_ref", "synth_reads", "synth_pool_reads", "synth_zipf_reads", "zipf_cdf",
            "GpuCounter",
-           "raise_read_error", "first_bad_buffer", "fastq_index", "gather_rows", "slice_fixed",
+           "raise_read_error", "first_bad_buffer", "fastq_index", "gather_rows", "trim_adapter", "host_trim_adapter",
+           "slice_fixed",
            "slice_var", "hamming_all_pairs", "hamming_nearest", "cluster_pairs", "umi_cluster",
            "GROUPED_ROW_TILE", "hamming_all_pairs_grouped", "umi_cluster_grouped", "HostStager", "host_stager", "encode_host", "decode_host"]
 
@@ -459,15 +460,90 @@ def synth_ragged_pool_reads(n: int, seed: int, pool_seed: int, U: int, Lmin: int
     return blob, offs, lens
 
 
+def _adapter_bytes(adapter, min_overlap: int, err_div: int) -> bytes:
+    """The adapter as bytes (str: its ASCII), with the argument checks of the C ABI raised as ValueError."""
+    if isinstance(adapter, str):
+        adapter = adapter.encode("ascii")
+    adapter = bytes(adapter)
+    if not 1 <= len(adapter) <= 64:
+        raise ValueError("adapter of 1 .. 64 bytes expected")
+    if min_overlap < 1:
+        raise ValueError("min_overlap >= 1 expected")
+    if err_div < 0:
+        raise ValueError("err_div >= 0 expected")
+    return adapter
+
+
+def trim_adapter(blob: torch.Tensor, offsets: torch.Tensor, lens: torch.Tensor, adapter, *, min_overlap: int = 3,
+                 err_div: int = 10, out: Optional[torch.Tensor] = None, stats: bool = False, _reads_per_launch: int = 0):
+    """3' adapter trim of a ragged batch (one ss_trim_adapter3 launch): the new length of read i =
+    blob[offsets[i] : offsets[i] + lens[i]] is the least position p at which `adapter` (bytes or str, 1..64
+    bytes, 'N' = wildcard) matches with overlap ov = min(len(adapter), lens[i] - p) >= min_overlap and at
+    most ov // err_div mismatches (err_div 0: none), or lens[i].  Leftmost match, no indels; the read's
+    bytes are compared as they are.  Reads longer than 1024 keep their length.  No read is moved:
+    (offsets, new lens) feed encode_var / DeviceIngest.count as they are.  `out` may be `lens` itself.
+    stats=True also returns an int64 [2] tensor {reads shortened, bytes removed}."""
+    for t, nm in ((blob, "blob"), (offsets, "offsets"), (lens, "lens")):
+        _require_cuda(t, nm)
+    if offsets.dtype != torch.int64 or lens.dtype not in (torch.int32, torch.uint32) or blob.dtype != torch.uint8:
+        raise TypeError("blob uint8, offsets int64, lens int32 expected")
+    a = _adapter_bytes(adapter, min_overlap, err_div)
+    n = lens.numel()
+    if offsets.numel() != n:
+        raise ValueError("offsets and lens differ in length")
+    dev = blob.device
+    if out is None:
+        out = torch.empty_like(lens)
+    else:
+        _require_cuda(out, "out")
+        if out.dtype != lens.dtype or out.numel() != n:
+            raise ValueError("out must match lens")
+    st = torch.empty(2, dtype=torch.int64, device=dev) if stats else None
+    abuf = (C.c_uint8 * len(a)).from_buffer_copy(a)
+    check(lib().ss_trim_adapter3_ex(blob.data_ptr(), blob.numel(), offsets.data_ptr(), lens.data_ptr(), n, abuf, len(a),
+                                    min_overlap, err_div, out.data_ptr(), _ptr(st), _reads_per_launch, _stream(dev)),
+          "ss_trim_adapter3")
+    return (out, st) if stats else out
+
+
+def host_trim_adapter(blob, offsets, lens, adapter, *, min_overlap: int = 3, err_div: int = 10, out=None,
+                      stats: bool = False):
+    """trim_adapter on numpy arrays (ss_host_trim_adapter3, plain C++): blob uint8, offsets uint64 / int64,
+    lens uint32 / int32.  Also checks that every read of at most 1024 bytes lies inside the blob."""
+    blob = np.ascontiguousarray(blob, dtype=np.uint8)
+    offsets = np.ascontiguousarray(offsets)
+    lens = np.ascontiguousarray(lens)
+    if offsets.dtype not in (np.uint64, np.int64) or lens.dtype not in (np.uint32, np.int32):
+        raise TypeError("blob uint8, offsets uint64, lens uint32 expected")
+    a = _adapter_bytes(adapter, min_overlap, err_div)
+    n = lens.size
+    if offsets.size != n:
+        raise ValueError("offsets and lens differ in length")
+    if out is None:
+        out = np.empty_like(lens)
+    elif out.dtype != lens.dtype or out.size != n or not out.flags.c_contiguous:
+        raise ValueError("out must match lens")
+    st = np.zeros(2, dtype=np.uint64) if stats else None
+    abuf = (C.c_uint8 * len(a)).from_buffer_copy(a)
+    check(lib().ss_host_trim_adapter3(blob.ctypes.data, blob.size, offsets.ctypes.data, lens.ctypes.data, n, abuf, len(a),
+                                      min_overlap, err_div, out.ctypes.data, st.ctypes.data if stats else None),
+          "ss_host_trim_adapter3")
+    return (out, st) if stats else out
+
+
 class DeviceIngest:
     """The drop-in counter's engine (ss_ingest_*) fed from device memory: count(blob, offsets, lens)
     any number of times (global read indices continue), then results() -> (lens u32, counts u64,
     words u64) numpy arrays in first-occurrence order (the ShortSeqCounter dict order: row k has
     ceil(lens[k] / 32) words, one for lengths 0..32).  A rejected read raises like ShortSeqCounter."""
 
-    def __init__(self, device=None, exact: bool = False, *, compact=True, _sizing: Optional[int] = None):
+    def __init__(self, device=None, exact: bool = False, *, compact=True, _sizing: Optional[int] = None,
+                 adapter=None, min_overlap: int = 3, err_div: int = 10):
         """compact: the rows cross PCIe with u16 lengths and u32 counts (u64 when a count needs it):
-        results() then returns those dtypes (ss_ingest_set_results_format)."""
+        results() then returns those dtypes (ss_ingest_set_results_format).
+        adapter (bytes or str): every batch is 3'-trimmed on the device first (the rule of trim_adapter,
+        ss_ingest_set_adapter); the caller's lens tensor is not written."""
+        a = None if adapter is None else _adapter_bytes(adapter, min_overlap, err_div)
         dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         self.device = dev
         h = C.c_void_p()
@@ -479,6 +555,9 @@ class DeviceIngest:
         self._sizing = int(exact) if _sizing is None else _sizing   # 2: test hook, undersized class tables
         self._fresh = True
         check(lib().ss_ingest_set_exact(h, self._sizing), "ss_ingest_set_exact")
+        if a is not None:
+            check(lib().ss_ingest_set_adapter(h, (C.c_uint8 * len(a)).from_buffer_copy(a), len(a), min_overlap, err_div),
+                  "ss_ingest_set_adapter")
 
     def count(self, blob: torch.Tensor, offsets: torch.Tensor, lens: torch.Tensor) -> None:
         for t, name in ((blob, "blob"), (offsets, "offsets"), (lens, "lens")):

@@ -77,6 +77,7 @@ ctypedef int (*f_get_device)(int*) noexcept nogil
 ctypedef int (*f_fastq_split)(const char*, uint32_t, uint64_t*, uint64_t*) noexcept nogil
 ctypedef int (*f_add_fastq_range)(ss_ingest*, const char*, uint64_t, uint64_t, uint64_t, uint64_t, uint64_t*) noexcept nogil
 ctypedef int (*f_set_exact)(ss_ingest*, int) noexcept nogil
+ctypedef int (*f_set_adapter)(ss_ingest*, const uint8_t*, uint32_t, uint32_t, uint32_t) noexcept nogil
 ctypedef int (*f_export)(ss_ingest*, uint64_t*) noexcept nogil
 ctypedef int (*f_merge)(ss_ingest*, ss_ingest*, uint64_t) noexcept nogil
 ctypedef int (*f_reserve_merge)(ss_ingest*, ss_ingest**, uint32_t) noexcept nogil
@@ -97,6 +98,7 @@ cdef struct _Abi:
     f_fastq_split fastq_split
     f_add_fastq_range add_fastq_range
     f_set_exact set_exact
+    f_set_adapter set_adapter
     f_export export_keys
     f_merge merge
     f_reserve_merge reserve_merge
@@ -135,6 +137,7 @@ cdef int _bind_abi() except -1:
     _abi.fastq_split = <f_fastq_split>_sym(h, b"ss_fastq_split")
     _abi.add_fastq_range = <f_add_fastq_range>_sym(h, b"ss_ingest_add_fastq_range")
     _abi.set_exact = <f_set_exact>_sym(h, b"ss_ingest_set_exact")
+    _abi.set_adapter = <f_set_adapter>_sym(h, b"ss_ingest_set_adapter")
     _abi.export_keys = <f_export>_sym(h, b"ss_ingest_export")
     _abi.merge = <f_merge>_sym(h, b"ss_ingest_merge")
     _abi.reserve_merge = <f_reserve_merge>_sym(h, b"ss_ingest_reserve_merge")
@@ -151,6 +154,13 @@ cdef extern from "host_codec.h":
     int ssh_encode "ssh::encode"(const uint8_t* s, size_t L, uint64_t* words, ss_err* err) nogil
     void ssh_decode "ssh::decode"(const uint64_t* words, size_t L, char* out) nogil
     uint64_t ssh_hamming "ssh::hamming"(const uint64_t* a, const uint64_t* b, size_t L) nogil
+
+cdef extern from "host_trim.h":
+    ctypedef struct ssh_TrimAdapter "ssh::TrimAdapter":
+        pass
+    bint ssh_trim_prepare "ssh::trim_prepare"(ssh_TrimAdapter* t, const uint8_t* a, uint32_t A, uint32_t min_overlap,
+                                              uint32_t err_div) nogil
+    uint32_t ssh_trim_read "ssh::trim_read"(const ssh_TrimAdapter& t, const uint8_t* r, uint32_t L) nogil
 
 # Domain constants (short_seq_64.pyx:27-28, short_seq_192.pyx:21-22, short_seq_var.pyx:8-10)
 MIN_64_NT = 0
@@ -953,18 +963,42 @@ def _raise_first_error(list reads, Py_ssize_t upto):
         _from_py_bytes(item)
 
 
-def read_and_count_fastq(filename, device="auto", *, _chunk_bytes=0):
+cdef bytes _adapter_arg(adapter, min_overlap, err_div):
+    """The adapter option of read_and_count_fastq as bytes, checked as the C ABI checks it."""
+    if isinstance(adapter, str):
+        adapter = adapter.encode("ascii")
+    if not isinstance(adapter, bytes):
+        raise TypeError(f"adapter: bytes or str expected, {type(adapter).__name__} found")
+    if not 1 <= len(adapter) <= 64:
+        raise ValueError("adapter of 1 .. 64 bytes expected")
+    if min_overlap < 1:
+        raise ValueError("min_overlap >= 1 expected")
+    if err_div < 0:
+        raise ValueError("err_div >= 0 expected")
+    return adapter
+
+
+def read_and_count_fastq(filename, device="auto", *, adapter=None, min_overlap=3, err_div=10, _chunk_bytes=0):
     """counter.pyx:57-70 + fast_read.pyx:3-20: keep line 2 of every 4 lines; each kept line loses
     exactly its last character (strlen - 1, short_seq.pyx:50-52); prints the reference's timings.
     device "auto" (the current GPU) / "cuda[:N]" / "all" / a list: the file is cut into one byte
     range per device at line boundaries (ss_fastq_split), each range streamed to its device in
     pinned chunks and indexed, split by length and counted there (ss_ingest_add_fastq_range), the
     ranges concurrently, and the dict built from the ranges' rows in file order; "host": the
-    reference's per-line loop."""
+    reference's per-line loop.
+    adapter (bytes or str, 1..64 bytes, 'N' = wildcard; keyword-only, not in the reference): every
+    sequence line is cut at the leftmost position where the adapter matches with an overlap of at
+    least min_overlap and at most overlap // err_div mismatches (no indels, not best-scoring;
+    include/shortseq_amd.h, "3' adapter trim") before it is counted -- on the device for the GPU paths,
+    with csrc/host_trim.h for "host".  A read is judged on its kept prefix only."""
     import os
+    cdef bytes ad = None if adapter is None else _adapter_arg(adapter, min_overlap, err_div)
+    cdef ssh_TrimAdapter trim
     devs = _resolve_devices(device)
     if devs:
-        return _read_and_count_fastq_gpu(filename, devs, _chunk_bytes)
+        return _read_and_count_fastq_gpu(filename, devs, _chunk_bytes, ad, min_overlap, err_div)
+    if ad is not None:
+        ssh_trim_prepare(&trim, <const uint8_t*>PyBytes_AS_STRING(ad), <uint32_t>len(ad), min_overlap, err_div)
     cdef FILE* f
     cdef char* line = NULL
     cdef size_t cap = 0
@@ -986,7 +1020,10 @@ def read_and_count_fastq(filename, device="auto", *, _chunk_bytes=0):
                 ln = strlen(line)
                 if ln == 0:   # strlen - 1 underflows in the reference -> the too-long error
                     raise Exception(f"Sequences longer than {MAX_VAR_NT} bases are not supported.")
-                seqs.append(PyBytes_FromStringAndSize(line, ln - 1))
+                ln -= 1
+                if ad is not None and ln <= C_MAX_VAR:
+                    ln = ssh_trim_read(trim, <const uint8_t*>line, <uint32_t>ln)
+                seqs.append(PyBytes_FromStringAndSize(line, ln))
             count += 1
     finally:
         fclose(f)
@@ -1008,11 +1045,13 @@ def fastq_stage_times():
     return [dict(x) for x in _last_fastq_stages]
 
 
-def _read_and_count_fastq_gpu(filename, devs, uint64_t chunk_bytes=0):
+def _read_and_count_fastq_gpu(filename, devs, uint64_t chunk_bytes=0, bytes adapter=None, uint32_t min_overlap=3,
+                              uint32_t err_div=10):
     """The file streamed through one engine per device: range k of ss_fastq_split on devs[k]
     (parallel preads into pinned staging, chunks ending after a newline, one-read FASTQ index, split
     by length and counted on the device); the ranges reduced on the devices in range order
-    (_reduce_fill)."""
+    (_reduce_fill).  With `adapter` every engine taken trims its chunks' lengths after the index
+    (ss_ingest_set_adapter); the engines are pooled, so the setting is cleared before they go back."""
     import os
     cdef int rc
     cdef Py_ssize_t D = len(devs), k
@@ -1039,6 +1078,9 @@ def _read_and_count_fastq_gpu(filename, devs, uint64_t chunk_bytes=0):
         for k in range(D):
             g = <size_t>_engine(devs[k])
             engines.append((devs[k], g))
+            if adapter is not None:
+                _ingest_check(_abi.set_adapter(<ss_ingest*><size_t>g, <const uint8_t*>PyBytes_AS_STRING(adapter),
+                                               <uint32_t>len(adapter), min_overlap, err_div), "ingest set adapter")
             if _abi.fq_stages != NULL:
                 _abi.fq_stages(<ss_ingest*><size_t>g, st_ms, &st_bytes)     # (drop what earlier calls left)
             jobs.append((g, 1, 0, 0, 0, fname, begin[k], begin[k + 1], line0[k], chunk_bytes, None))
@@ -1062,6 +1104,8 @@ def _read_and_count_fastq_gpu(filename, devs, uint64_t chunk_bytes=0):
         free(line0)
         for d, h in engines:
             _engine_nkeys.pop(h, None)
+            if adapter is not None:      # (also on an engine that was counted again after SS_EFULL)
+                _abi.set_adapter(<ss_ingest*><size_t>h, NULL, 0, 0, 0)
             _engine_release(d, <ss_ingest*><size_t>h)
     print(f"{t2-t1:.2f}s to read {nseqs} total seqs, and {t3 - t2:.2f}s to count {len(counts)} unique sequences")
     return counts

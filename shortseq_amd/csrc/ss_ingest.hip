@@ -929,6 +929,10 @@ struct ss_ingest {
     bool failed = false;           // an add returned SS_EFULL: the counts are void until reset
     int sizing = 0;                // class tables: 0 by their sketch, 1 by their rows, 2 by 1/64 of the
                                    // sketch (tests: forces the SS_EFULL path) -- ss_ingest_set_exact
+    // 3' adapter (ss_ingest_set_adapter; adapter_len == 0: none): every chunk's lengths are trimmed once
+    // on the stream before process_chunk sees them (trim_chunk)
+    uint8_t adapter[64] = {};
+    uint32_t adapter_len = 0, adapter_min_overlap = 0, adapter_err_div = 0;
     DBuf<uint64_t> first_bad;      // [kLenBins + 1]: one u64 per length bin, the class encode's last
     uint64_t* h_bad = nullptr;     // pinned [3 kLenBins + 8]: first-bad and overflow words, a size query
     std::map<uint32_t, Group> groups;
@@ -1953,6 +1957,14 @@ int index_chunk(ss_ingest* g, const uint8_t* d_buf, uint64_t use, uint64_t line0
     }
 }
 
+// The engine's adapter applied to a chunk's lengths (ss_trim_adapter3 on the engine's stream): d_out
+// may be d_lens (in place).  Only called with an adapter set.
+int trim_chunk(ss_ingest* g, const uint8_t* d_buf, uint64_t nbytes, const uint64_t* d_offs, const uint32_t* d_lens,
+               uint64_t n, uint32_t* d_out) {
+    return ss_trim_adapter3(d_buf, nbytes, d_offs, d_lens, n, g->adapter, g->adapter_len, g->adapter_min_overlap,
+                            g->adapter_err_div, d_out, nullptr, g->stream);
+}
+
 // the file descriptor of one call, closed however the call ends
 struct Fd {
     const int v;
@@ -2055,6 +2067,17 @@ int ss_ingest_set_exact(ss_ingest* g, int exact) {
     return SS_OK;
 }
 
+int ss_ingest_set_adapter(ss_ingest* g, const uint8_t* h_adapter, uint32_t A, uint32_t min_overlap, uint32_t err_div) {
+    if (!g) return ss_fail(SS_EARG, "null ingest");
+    if (A > sizeof(g->adapter)) return ss_fail(SS_EARG, "ingest: adapter length 0 .. 64");
+    if (A && (!h_adapter || min_overlap == 0)) return ss_fail(SS_EARG, "ingest: adapter needs its bytes and min_overlap >= 1");
+    if (A) memcpy(g->adapter, h_adapter, A);
+    g->adapter_len = A;
+    g->adapter_min_overlap = min_overlap;
+    g->adapter_err_div = err_div;
+    return SS_OK;
+}
+
 int ss_ingest_destroy(ss_ingest* g) {
     if (!g) return SS_OK;
     ss_ingest_reset(g);
@@ -2120,11 +2143,13 @@ int ss_ingest_add_blob(ss_ingest* g, const uint8_t* h_blob, const uint32_t* h_le
     int rc;
     if ((rc = g->dbuf.ensure(total + 16)) || (rc = g->offs.ensure(n)) || (rc = g->dlens.ensure(n))) return rc;
     rc = ss_check(hipMemcpyAsync(g->dbuf.p, h_blob, total ? total : 1, hipMemcpyHostToDevice, s), "ingest H2D");
-    const uint32_t dense = (same && h_lens[0] > 0 && h_lens[0] <= SS_MAX_NT) ? h_lens[0] : 0u;
+    // (with an adapter the lengths no longer agree after the trim: never a dense chunk)
+    const uint32_t dense = (!g->adapter_len && same && h_lens[0] > 0 && h_lens[0] <= SS_MAX_NT) ? h_lens[0] : 0u;
     if (!rc && !dense) {
         rc = ss_check(hipMemcpyAsync(g->offs.p, offs.data(), n * 8, hipMemcpyHostToDevice, s), "ingest H2D");
         if (!rc) rc = ss_check(hipMemcpyAsync(g->dlens.p, h_lens, n * 4, hipMemcpyHostToDevice, s), "ingest H2D");
     }
+    if (!rc && g->adapter_len) rc = trim_chunk(g, g->dbuf.p, total, g->offs.p, g->dlens.p, n, g->dlens.p);
     if (!rc) rc = process_chunk(g, {g->dbuf.p, g->offs.p, g->dlens.p, total, n, dense, &offs, h_blob, true});
     if (!rc) rc = ss_check(hipStreamSynchronize(s), "ingest blob");   // staging reusable after return
     return rc;
@@ -2135,7 +2160,13 @@ int ss_ingest_add_device(ss_ingest* g, const uint8_t* d_blob, uint64_t nbytes, c
     if (!g || (n && (!d_blob || !d_offsets || !d_lens))) return ss_fail(SS_EARG, "null argument");
     if (n == 0 || g->bad_index != kNoSlot) return SS_OK;
     (void)hipSetDevice(g->device);
-    int rc = process_chunk(g, {d_blob, d_offsets, d_lens, nbytes, n, 0, nullptr, nullptr, true});
+    int rc = SS_OK;
+    if (g->adapter_len) {      // trimmed into the engine's own lengths: the caller's are const
+        if (n >= (1ull << 32)) return ss_fail(SS_EARG, "ingest: a chunk holds < 2^32 reads");
+        if ((rc = g->dlens.ensure(n)) || (rc = trim_chunk(g, d_blob, nbytes, d_offsets, d_lens, n, g->dlens.p))) return rc;
+        d_lens = g->dlens.p;
+    }
+    rc = process_chunk(g, {d_blob, d_offsets, d_lens, nbytes, n, 0, nullptr, nullptr, true});
     if (!rc) rc = ss_check(hipStreamSynchronize(g->stream), "ingest device blob");
     return rc;
 }
@@ -2233,6 +2264,10 @@ int ss_ingest_add_fastq_range(ss_ingest* g, const char* path, uint64_t begin, ui
         uint64_t nl = 0, nrec = 0;
         rc = ss_check(hipStreamWaitEvent(s, sl.done, 0), "ingest fastq wait");
         if (!rc) rc = index_chunk(g, sl.d.p, c.use, line0, c.at_eof, &nl, &nrec);
+        if (!rc && g->adapter_len && nrec) {     // in place, and waited for: the trim is part of the index stage
+            rc = trim_chunk(g, sl.d.p, c.use, g->offs.p, g->dlens.p, nrec, g->dlens.p);
+            if (!rc) rc = ss_check(hipStreamSynchronize(s), "ingest fq trim");
+        }
         if (rc) break;
         fq.ms[2] += since(ti);
         fq.ms[1] += fq.pieces_ms(k & 1, c.np);     // (all complete: the index synced)

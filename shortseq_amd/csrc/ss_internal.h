@@ -61,6 +61,13 @@ extern "C" int ss_counter_insert_keys(ss_counter* c, const uint64_t* d_keys, uin
 // 8 = two exact scatter passes, 16 = histogram by k_pc_keys (else k_pc_hist), bits 5-6 the
 // optimistic coarse kernel (0 plain, 1 G16, 2 keys), 128 = fine-scatter slabs (else counted cursors).
 extern "C" int ss_counter_last_route(const ss_counter* c);
+// ss_trim_adapter3_ex with the kernel's shape open (tools/probe_trim.py measures the variants): group =
+// lanes per read (2, 4, 8, 16 or 32; 0 = the library's), staged = 1 the read's chunks through LDS, 0 aligned
+// dword loads straight from global memory, < 0 the library's.  Same results for every shape.
+extern "C" int ss_trim_adapter3_shape(const uint8_t* d_blob, uint64_t nbytes, const uint64_t* d_offsets,
+                                      const uint32_t* d_lens, uint64_t n, const uint8_t* h_adapter, uint32_t A,
+                                      uint32_t min_overlap, uint32_t err_div, uint32_t* d_out_lens, uint64_t* d_stats,
+                                      uint64_t reads_per_launch, uint32_t group, int staged, void* stream);
 // One length class of the drop-in engine's chunk for ss_classes_verify_fold: its table (set_words(W1)),
 // its m packed rows of W1 words, and the table's first row index for them.
 struct ss_class_rows {
