@@ -21,7 +21,7 @@ LIB = os.path.join(PKG, "lib", "libshortseq_amd.so")
 HIP_SOURCES = ["ss_codec.hip", "ss_counter.hip", "ss_fastq.hip", "ss_allpairs.hip", "ss_runtime.hip", "ss_ingest.hip",
                "ss_stage.hip", "ss_cluster.hip", "ss_nearest.hip", "ss_grouped.hip", "ss_trim.hip"]
 HIP_DEPS = HIP_SOURCES + ["ss_device.h", "ss_hamming.h", "ss_internal.h", "host_codec.h", "fq_reader.h",
-                          "host_threads.h", "host_trim.h"]
+                          "host_threads.h", "host_trim.h", "ss_owned.h"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = os.environ.get("SHORTSEQ_AMD_ARCH", "gfx950")
 

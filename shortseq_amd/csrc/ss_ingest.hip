@@ -41,6 +41,7 @@
 #include <sys/stat.h>
 #include <unistd.h>
 
+#include <stddef.h>
 #include <string.h>
 
 #include <algorithm>
@@ -706,88 +707,19 @@ uint64_t pow2_at_least(uint64_t x) {
     return p;
 }
 
-// grow-only device buffer
-template <typename T>
-struct DBuf {
-    T* p = nullptr;
-    uint64_t cap = 0;
-    int ensure(uint64_t n) {
-        if (n <= cap) return SS_OK;
-        if (p) {
-            (void)hipDeviceSynchronize();   // queued work may still read the old buffer
-            (void)hipFree(p);
-        }
-        p = nullptr;
-        cap = 0;
-        const uint64_t want = std::max<uint64_t>(n, 1024);
-        if (hipMalloc((void**)&p, want * sizeof(T)) != hipSuccess) {
-            (void)hipGetLastError();
-            return ss_fail(SS_ENOMEM, "ingest: out of device memory");
-        }
-        cap = want;
-        return SS_OK;
-    }
-    // grow keeping the first `used` elements (geometric: appended-to buffers such as row maps)
-    int ensure_keep(uint64_t n, uint64_t used, hipStream_t s) {
-        if (n <= cap) return SS_OK;
-        T* q = nullptr;
-        const uint64_t want = std::max<uint64_t>(n, 2 * cap);
-        if (hipMalloc((void**)&q, want * sizeof(T)) != hipSuccess) {
-            (void)hipGetLastError();
-            return ss_fail(SS_ENOMEM, "ingest: out of device memory");
-        }
-        int rc = SS_OK;
-        if (used) rc = ss_check(hipMemcpyAsync(q, p, used * sizeof(T), hipMemcpyDeviceToDevice, s), "ingest grow copy");
-        if (!rc) rc = ss_check(hipStreamSynchronize(s), "ingest grow copy");
-        if (p) (void)hipFree(p);
-        p = q;
-        cap = want;
-        return rc;
-    }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-};
-
-// grow-only pinned host buffer
-struct HBuf {
-    uint8_t* p = nullptr;
-    uint64_t cap = 0;
-    int ensure(uint64_t n) {
-        if (n <= cap) return SS_OK;
-        if (p) (void)hipHostFree(p);
-        p = nullptr;
-        cap = 0;
-        const uint64_t want = std::max<uint64_t>(n, 1 << 20);
-        if (hipHostMalloc((void**)&p, want, hipHostMallocDefault) != hipSuccess) {
-            (void)hipGetLastError();
-            return ss_fail(SS_ENOMEM, "ingest: out of pinned host memory");
-        }
-        cap = want;
-        return SS_OK;
-    }
-    void release() {
-        if (p) (void)hipHostFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-};
-
 // The engine's side of the FASTQ reader ring (fq_reader.h; ss_ingest_add_fastq_range): the two slots'
 // buffers -- a slot is one chunk, pinned and on the device -- the copy stream and the stage split,
 // driven by the reader through FqSlotOps.
 constexpr uint64_t kFqChunkDefault = 1ull << 30;     // chunk bytes when the caller passes 0
 struct FqState final : FqSlotOps {
+    int device = 0;
+    Stream copy;                      // the reader thread's H2D pieces
     struct Slot {
         HBuf h;
         DBuf<uint8_t> d;
-        hipEvent_t done = nullptr;    // the slot's H2D pieces are complete (recorded on copy)
-        std::vector<hipEvent_t> ev;   // 2 timing events per H2D piece
+        Event done;                   // the slot's H2D pieces are complete (recorded on copy)
+        std::vector<Event> ev;        // 2 timing events per H2D piece
     } slot[2];
-    int device = 0;
-    hipStream_t copy = nullptr;       // the reader thread's H2D pieces
     // the reader thread's CPUs: the GPU's NUMA node's (ss_gpu_numa_cpus; looked up once, node -2
     // until then), so the pinned slots it allocates and the file bytes it copies in are node-local
     std::vector<int> cpus;
@@ -803,9 +735,9 @@ struct FqState final : FqSlotOps {
     int prepare(int dev) {
         device = dev;
         int rc = SS_OK;
-        if (!copy) rc = ss_check(hipStreamCreateWithFlags(&copy, hipStreamNonBlocking), "ingest fastq stream");
+        if (!copy) rc = ss_check(hipStreamCreateWithFlags(copy.put(), hipStreamNonBlocking), "ingest fastq stream");
         for (int i = 0; i < 2 && !rc; ++i)
-            if (!slot[i].done) rc = ss_check(hipEventCreateWithFlags(&slot[i].done, hipEventDisableTiming), "ingest fastq event");
+            if (!slot[i].done) rc = ss_check(hipEventCreateWithFlags(slot[i].done.put(), hipEventDisableTiming), "ingest fastq event");
         if (node == -2) {
             int allowed = 0;
             cpus = ss_gpu_numa_cpus(device, &node, &allowed);
@@ -813,18 +745,6 @@ struct FqState final : FqSlotOps {
             if (env && env[0] == '0') cpus.clear();
         }
         return rc;
-    }
-    void release() {
-        for (Slot& sl : slot) {
-            for (hipEvent_t e : sl.ev) (void)hipEventDestroy(e);
-            sl.ev.clear();
-            if (sl.done) (void)hipEventDestroy(sl.done);
-            sl.done = nullptr;
-            sl.h.release(), sl.d.release();
-        }
-        if (copy) (void)hipStreamDestroy(copy);
-        copy = nullptr;
-        ws.release(), aux.release(), counts.release();
     }
     // the summed device ms of the first np H2D pieces of slot i (all complete)
     double pieces_ms(int i, uint32_t np) const {
@@ -848,10 +768,9 @@ struct FqState final : FqSlotOps {
         Slot& sl = slot[i];
         // (a piece number's first use only: the events stay with the slot)
         while (sl.ev.size() < 2 * (piece + 1)) {
-            sl.ev.reserve(sl.ev.size() + 2);      // so that no event is lost to a failed push_back
-            hipEvent_t e = nullptr;
-            if (int rc = ss_check(hipEventCreate(&e), "ingest fastq event")) return rc;
-            sl.ev.push_back(e);
+            Event e;
+            if (int rc = ss_check(hipEventCreate(e.put()), "ingest fastq event")) return rc;
+            sl.ev.push_back(std::move(e));
         }
         int rc = ss_check(hipEventRecord(sl.ev[2 * piece], copy), "ingest fastq event");
         if (!rc) rc = ss_check(hipMemcpyAsync(sl.d.p + off, sl.h.p + off, len, hipMemcpyHostToDevice, copy), "ingest H2D");
@@ -864,19 +783,54 @@ struct FqState final : FqSlotOps {
         HBuf grown;
         if (int rc = grown.ensure(cap)) return rc;
         memcpy(grown.p, slot[i].h.p, keep);
-        slot[i].h.release();
-        slot[i].h = grown;
-        *host = grown.p;
+        slot[i].h = std::move(grown);
+        *host = slot[i].h.p;
         return SS_OK;
     }
     int complete(int i) override { return ss_check(hipEventRecord(slot[i].done, copy), "ingest fastq event"); }
     const char* last_error() override { return ss_last_error_string(); }
 };
 
+using Table = Handle<ss_counter*, ss_counter_destroy>;
+
+struct ExtractCount {                   // an extraction's device words, one triple per group
+    uint64_t count, overflow, spare;
+};
+// The small results the device hands back, pinned: one region per purpose, none shared.
+struct HostWords {
+    uint64_t first_bad[kLenBins + 1];   // collect_chunk: per length bin, the class encode's last
+    uint64_t ovf[kLenBins + 1];         // collect_chunk / flush_pending: per job, the scratch table's last
+    uint32_t fp_flag, fp_pad;           // collect_chunk: two keys share a fingerprint
+    ExtractCount extract[kLenBins];     // extract_groups: per group placed
+    uint64_t table_size, rekey_count;   // table_size; group_rekey: the entries extracted
+    uint64_t fq_counts[3], export_max;  // index_chunk: newlines, records, overflow; ss_ingest_export: the largest count
+};
+struct DevWords {                       // the device sides of those that have no buffer of their own
+    ExtractCount extract[kLenBins];     // (sized by kLenBins: a group per length bin at the most)
+    uint64_t table_size, rekey_count;
+};
+// the scans' block sums and, behind them, k_scan_top's total (the word total of OutLayout::dNW)
+struct ScanWords {
+    uint64_t blksum[kScanBlocks], total, spare;
+};
+// The speculative finish's device words; k_spec_total knows them by index
+struct SpecSizes {
+    uint64_t K, NW, bad, max_count;     // entries, words, gather bad | extract overflow, the largest count
+};
+struct SpecWords {
+    uint64_t cls[6];                    // class W's entry total at cls[W] (W = 2 .. 5)
+    uint64_t K, gather_bad, extract_ovf;    // K: their sum + the empty read's entry
+    SpecSizes out;                      // one copy of it reaches the host's SpecSizes
+};
+static_assert(offsetof(ScanWords, total) == kScanBlocks * 8 && offsetof(SpecWords, K) == 6 * 8 &&
+                  offsetof(SpecWords, gather_bad) == 7 * 8 && offsetof(SpecWords, extract_ovf) == 8 * 8 &&
+                  offsetof(SpecWords, out) == 9 * 8 && sizeof(SpecWords) == 13 * 8,
+              "k_scan_top's and k_spec_total's indices; one hipMemsetAsync clears all of SpecWords");
+
 struct Group {
     uint32_t L = 0;               // 1..32: the length of every key; 0: a length class
     uint32_t W1 = 1;              // words per table key: 1, or a class's ceil(L/32) + 1 (length word)
-    ss_counter* table = nullptr;
+    Table table;
     uint64_t cap = 0;
     uint64_t rows = 0;            // rows inserted (= the table's first index space)
     DBuf<uint64_t> rowmap;        // row -> global read index (the table's first index is the row)
@@ -893,12 +847,14 @@ struct Group {
 
 struct ss_ingest {
     int device = 0;
-    hipStream_t stream = nullptr;
+    // (the streams first: members go in reverse order, so buffers are freed before the streams they ran on)
+    Stream stream;
     // the length classes' table inserts run on up to kSide + 1 streams (independent tables: one
     // class's short partition kernels and aggregate tail overlap another's); forked / joined by events
     static constexpr int kSide = 2;
-    hipStream_t side[kSide] = {};
-    hipEvent_t ev_fork = nullptr, ev_join[kSide] = {};
+    Stream side[kSide];
+    Stream spec_stream;            // the speculative finish (below)
+    Event ev_fork, ev_join[kSide];
     HBuf stage;                    // list bytes / FASTQ chunks (pinned)
     HBuf out_host;                 // results: lens | counts | words (pinned)
     DBuf<uint8_t> dbuf;            // the chunk on the device
@@ -907,7 +863,7 @@ struct ss_ingest {
     DBuf<uint64_t> order;          // split output
     DBuf<uint32_t> blkhist, blkfirst;
     DBuf<uint64_t> split_out;      // [3 * kLenBins + 1]: totals, first reads, starts, the read-order stride
-    uint64_t* h_split = nullptr;   // pinned copy
+    Pinned<uint64_t> h_split;      // pinned copy
     // the previous chunk's read-order stride (0: it took another path): the next chunk's row encode is
     // queued at that stride before its split comes back (process_chunk); flat_streak = how many chunks
     // in a row took the read-order path at that stride
@@ -917,14 +873,14 @@ struct ss_ingest {
     bool defer_prep = false;
     std::vector<unsigned long long*> prep_p;
     std::vector<unsigned long long> prep_v;
-    hipEvent_t ev_split = nullptr;
+    Event ev_split;
     DBuf<uint8_t> rows;            // gathered dense rows (lengths <= 32)
     DBuf<uint64_t> cls_words;      // the length classes' packed rows (k_encode_classes / k_encode_class)
     DBuf<uint64_t> cls_fps;        // their fingerprints (k_encode_classes), class after class
-    ss_counter* fpt = nullptr;     // the classes' rows counted by fingerprint (single-word scratch table)
+    Table fpt;                     // the classes' rows counted by fingerprint (single-word scratch table)
     DBuf<uint32_t> cls_flag;       // set by ss_classes_verify_fold: two keys share a fingerprint
     DBuf<uint32_t> hll;            // per class W: 2^kHllLog HyperLogLog registers over the call
-    uint32_t* h_hll = nullptr;     // pinned copy
+    Pinned<uint32_t> h_hll;        // pinned copy
     DBuf<uint64_t> ovf;            // per job: its table's overflow word after the insert
     bool failed = false;           // an add returned SS_EFULL: the counts are void until reset
     int sizing = 0;                // class tables: 0 by their sketch, 1 by their rows, 2 by 1/64 of the
@@ -934,9 +890,10 @@ struct ss_ingest {
     uint8_t adapter[64] = {};
     uint32_t adapter_len = 0, adapter_min_overlap = 0, adapter_err_div = 0;
     DBuf<uint64_t> first_bad;      // [kLenBins + 1]: one u64 per length bin, the class encode's last
-    uint64_t* h_bad = nullptr;     // pinned [3 kLenBins + 8]: first-bad and overflow words, a size query
+    Pinned<HostWords> hw;          // pinned: every small result the device hands back
+    Buf<DevWords, DevMem> dw;      // on the device: the count triples, the size query's and the re-key's word
     std::map<uint32_t, Group> groups;
-    std::vector<std::pair<uint64_t, ss_counter*>> pool;    // idle tables (capacity, handle)
+    std::vector<std::pair<uint64_t, Table>> pool;          // idle tables (capacity, handle)
     uint64_t nreads = 0;           // global read index of the next read
     uint64_t empty_count = 0, empty_first = kNoSlot;
     // first rejected read (input order)
@@ -967,21 +924,21 @@ struct ss_ingest {
     // ss_ingest_finish then only waits for it; any other call waits for it first (spec_wait) and
     // drops it.  A verify that flags a shared fingerprint, a rejected read, or a result larger than
     // the bound it was given invalidates it (the finish then runs the ordinary way).
-    hipStream_t spec_stream = nullptr;
-    hipEvent_t ev_reps = nullptr, ev_spec = nullptr;
+    Event ev_reps, ev_spec;
     bool spec_inflight = false;
     bool spec_valid = false;
-    DBuf<uint64_t> spec_dev;       // [12]: class totals [2..5], K [6], gather bad [7], extract overflow [8], K NW bad [9..11]
-    uint64_t* h_spec = nullptr;    // pinned [4]: K, NW, bad, the largest count
+    Buf<SpecWords, DevMem> spec_dev;
+    Pinned<SpecSizes> h_spec;      // pinned copy of spec_dev's `out`
     int compact = 0;               // ss_ingest_set_results_format: u16 lengths, u32 counts when they fit
     bool wide = false;             // compact results whose counts need u64
-    GDesc* h_gdesc = nullptr;      // pinned [8]
+    Pinned<GDesc> h_gdesc;         // pinned [8]
     // ss_ingest_merge scratch (this engine as the destination): a source group's entries on this device
     DBuf<uint64_t> mg_words, mg_counts, mg_first, mg_take;
     DBuf<uint32_t> mg_lens;
     // finish() results
     uint64_t nkeys = 0, nwords = 0;
-    DBuf<uint64_t> slot, ordered, woff, scan;
+    DBuf<uint64_t> slot, ordered, woff;
+    Buf<ScanWords, DevMem> scan;
     DBuf<GDesc> gdesc;
     FqState fq;                    // the FASTQ reader ring's slots, copy stream, index workspace, stage split
 };
@@ -1001,7 +958,7 @@ int queue_reset(ss_ingest* g, ss_counter* t) {
 // a pooled table of this capacity, preferring one whose key width W1 (its key-word array) and
 // partition workspace (rows) already fit: a mismatch reallocates them at the first insert (hipFree +
 // hipMalloc, 0.3-0.4 ms per class table on the f2 batch when two classes swapped tables of one size)
-int table_get(ss_ingest* g, uint64_t cap, uint32_t W1, uint64_t rows, ss_counter** out) {
+int table_get(ss_ingest* g, uint64_t cap, uint32_t W1, uint64_t rows, Table* out) {
     size_t best = g->pool.size();
     int best_score = -1;
     for (size_t i = g->pool.size(); i-- > 0;) {
@@ -1014,11 +971,11 @@ int table_get(ss_ingest* g, uint64_t cap, uint32_t W1, uint64_t rows, ss_counter
         }
     }
     if (best < g->pool.size()) {
-        *out = g->pool[best].second;
+        *out = std::move(g->pool[best].second);
         g->pool.erase(g->pool.begin() + (long)best);
         return g->defer_prep ? queue_reset(g, *out) : ss_counter_reset(*out, g->stream);
     }
-    return ss_counter_create(cap, out);
+    return ss_counter_create(cap, out->put());
 }
 
 // the queued reset words in one dispatch on the engine's stream (or several, past kPrepMany words)
@@ -1036,28 +993,24 @@ int flush_prep(ss_ingest* g) {
 // device bytes a pooled table holds: its slots and its partition workspace (~100 B per reserved read)
 uint64_t table_bytes(ss_counter* t) { return ss_counter_capacity(t) * 16 + ss_counter_reserved(t) * 100; }
 
-void table_put(ss_ingest* g, ss_counter* t) {
+void table_put(ss_ingest* g, Table&& t) {
     if (!t) return;
-    g->pool.emplace_back(ss_counter_capacity(t), t);   // workspace kept: the next call reuses it
+    g->pool.emplace_back(ss_counter_capacity(t), std::move(t));   // workspace kept: the next call reuses it
     uint64_t total = 0;
     for (auto& p : g->pool) total += table_bytes(p.second);
     while (!g->pool.empty() && total > (6ull << 30)) {
         total -= table_bytes(g->pool.front().second);
-        ss_counter_destroy(g->pool.front().second);
-        g->pool.erase(g->pool.begin());
+        g->pool.erase(g->pool.begin());      // (destroys the table)
     }
 }
 
 // size query (one sync): occupied slots of a table
 int table_size(ss_ingest* g, ss_counter* t, uint64_t* out) {
-    DBuf<uint64_t>& s = g->scan;
-    int rc = s.ensure(kScanBlocks + 8);
-    if (rc) return rc;
-    rc = ss_counter_size(t, s.p + kScanBlocks + 2, g->stream);
-    if (rc) return rc;
-    rc = ss_check(hipMemcpyAsync(g->h_bad + 2 * kLenBins + 2, s.p + kScanBlocks + 2, 8, hipMemcpyDeviceToHost, g->stream), "ingest size copy");
+    uint64_t* d_size = &g->dw.p->table_size;
+    int rc = ss_counter_size(t, d_size, g->stream);
+    if (!rc) rc = ss_check(hipMemcpyAsync(&g->hw.p->table_size, d_size, 8, hipMemcpyDeviceToHost, g->stream), "ingest size copy");
     if (!rc) rc = ss_check(hipStreamSynchronize(g->stream), "ingest sync");
-    *out = g->h_bad[2 * kLenBins + 2];
+    *out = g->hw.p->table_size;
     return rc;
 }
 
@@ -1090,6 +1043,14 @@ int table_kind(const Group& gr, ss_counter* t) {
     return gr.L ? ss_counter_set_length(t, gr.L == kShortL ? 32u : gr.L) : ss_counter_set_words(t, gr.W1);
 }
 
+// m entries merged into a table by its key kind: a single-word key travels with its length, a
+// packed-word key (W1 > 1) as its words (equality is decided on them)
+int table_merge(ss_counter* t, uint32_t W1, const uint64_t* words, const uint32_t* lens, const uint64_t* counts,
+                const uint64_t* first, uint64_t m, hipStream_t s) {
+    return W1 == 1 ? ss_counter_merge(t, words, lens, counts, first, m, s)
+                   : ss_counter_merge_words(t, words, counts, first, m, s);
+}
+
 // A group whose rows would pass the table's u32 first index (max_rows: 2^32 - 1 reads of one length
 // or class in one call) is re-keyed: its entries become its rows 0..K-1 (extract, then merge back
 // with first index = entry, the row map compacted to the entries' first reads), so one call counts
@@ -1098,16 +1059,16 @@ int group_rekey(ss_ingest* g, Group& gr) {
     hipStream_t s = g->stream;
     const uint64_t cap = gr.cap + 1;
     const uint32_t W = gr.W1;
-    int rc = g->scan.ensure(kScanBlocks + 2 + 2 * (uint64_t)kLenBins + 8);
-    if (rc || (rc = gr.fps.ensure(cap)) || (rc = gr.words.ensure(cap * W)) || (rc = gr.counts.ensure(cap)) ||
+    int rc;
+    if ((rc = gr.fps.ensure(cap)) || (rc = gr.words.ensure(cap * W)) || (rc = gr.counts.ensure(cap)) ||
         (rc = gr.first.ensure(cap)) || (rc = gr.lens.ensure(cap)))
         return rc;
-    uint64_t* d_cnt = g->scan.p + kScanBlocks + 2;
+    uint64_t* d_cnt = &g->dw.p->rekey_count;
     rc = ss_counter_extract_words(gr.table, 1, gr.fps.p, gr.lens.p, gr.words.p, gr.counts.p, gr.first.p, cap, d_cnt, s);
-    if (!rc) rc = ss_check(hipMemcpyAsync(g->h_bad, d_cnt, 8, hipMemcpyDeviceToHost, s), "ingest rekey count");
+    if (!rc) rc = ss_check(hipMemcpyAsync(&g->hw.p->rekey_count, d_cnt, 8, hipMemcpyDeviceToHost, s), "ingest rekey count");
     if (!rc) rc = ss_check(hipStreamSynchronize(s), "ingest rekey");
     if (rc) return rc;
-    const uint64_t m = g->h_bad[0];
+    const uint64_t m = g->hw.p->rekey_count;
     DBuf<uint64_t> nmap, nacc;
     if ((rc = nmap.ensure(std::max<uint64_t>(m, gr.rows)))) return rc;
     if (gr.acc_rows) {      // spilled counts follow their entries to the new rows
@@ -1119,19 +1080,12 @@ int group_rekey(ss_ingest* g, Group& gr) {
     if (m)
         hipLaunchKernelGGL(k_rekey, dim3(grid_of(m, 256)), dim3(256), 0, s, gr.first.p, m, gr.rowmap.p, nmap.p, gr.fps.p);
     if ((rc = ss_counter_reset(gr.table, s)) || (rc = table_kind(gr, gr.table))) return rc;
-    rc = W == 1 ? ss_counter_merge(gr.table, gr.words.p, gr.lens.p, gr.counts.p, gr.fps.p, m, s)
-                : ss_counter_merge_words(gr.table, gr.words.p, gr.counts.p, gr.fps.p, m, s);
+    rc = table_merge(gr.table, W, gr.words.p, gr.lens.p, gr.counts.p, gr.fps.p, m, s);
     if (!rc) rc = ss_check(hipStreamSynchronize(s), "ingest rekey merge");
     if (rc) return rc;
-    gr.rowmap.release();
-    gr.rowmap = nmap;
-    nmap.p = nullptr;
-    nmap.cap = 0;
+    gr.rowmap = std::move(nmap);
     if (gr.acc_rows) {
-        gr.acc.release();
-        gr.acc = nacc;
-        nacc.p = nullptr;
-        nacc.cap = 0;
+        gr.acc = std::move(nacc);
         gr.acc_rows = m;
     }
     gr.rows = m;
@@ -1181,13 +1135,12 @@ int group_room(ss_ingest* g, Group& gr, uint64_t m, uint64_t need) {
     need = std::min(need, size + m);
     if (need <= gr.cap / 2) return SS_OK;
     const uint64_t ncap = pow2_at_least(2 * need);
-    ss_counter* nt = nullptr;
+    Table nt;       // (owned here until it is the group's: an error on the way destroys it)
     const bool defer = g->defer_prep;     // (merged into at once: its reset goes out now)
     g->defer_prep = false;
     rc = table_get(g, ncap, gr.W1, m, &nt);
     g->defer_prep = defer;
-    if (rc != SS_OK) return rc;
-    if ((rc = table_kind(gr, nt)) != SS_OK) return rc;
+    if (rc || (rc = table_kind(gr, nt))) return rc;
     const uint64_t cap = gr.cap + 1;
     const uint32_t W = gr.W1;
     DBuf<uint64_t> k, c, f, pc, wd;
@@ -1195,19 +1148,14 @@ int group_room(ss_ingest* g, Group& gr, uint64_t m, uint64_t need) {
     if ((rc = k.ensure(cap)) || (rc = c.ensure(cap)) || (rc = f.ensure(cap)) || (rc = l.ensure(cap)) ||
         (rc = pc.ensure(1)) || (W > 1 && (rc = wd.ensure(cap * W))))
         return rc;
-    if (W == 1) {
-        rc = ss_counter_extract(gr.table, 1, k.p, l.p, c.p, f.p, cap, pc.p, g->stream);
-        if (!rc) rc = ss_counter_merge(nt, k.p, l.p, c.p, f.p, size, g->stream);
-    } else {     // packed-word keys: the entries' words travel (equality is decided on them)
-        rc = ss_counter_extract_words(gr.table, 1, k.p, l.p, wd.p, c.p, f.p, cap, pc.p, g->stream);
-        if (!rc) rc = ss_counter_merge_words(nt, wd.p, c.p, f.p, size, g->stream);
-    }
+    rc = W == 1 ? ss_counter_extract(gr.table, 1, k.p, l.p, c.p, f.p, cap, pc.p, g->stream)
+                : ss_counter_extract_words(gr.table, 1, k.p, l.p, wd.p, c.p, f.p, cap, pc.p, g->stream);
+    if (!rc) rc = table_merge(nt, W, W == 1 ? k.p : wd.p, l.p, c.p, f.p, size, g->stream);
     if (!rc) rc = ss_check(hipStreamSynchronize(g->stream), "ingest grow");
-    k.release(), c.release(), f.release(), l.release(), pc.release(), wd.release();
     if (rc) return rc;
-    table_put(g, gr.table);
-    gr.table = nt;
-    gr.cap = ss_counter_capacity(nt);
+    table_put(g, std::move(gr.table));
+    gr.table = std::move(nt);
+    gr.cap = ss_counter_capacity(gr.table);
     return SS_OK;
 }
 
@@ -1232,11 +1180,11 @@ int flush_pending(ss_ingest* g) {
     if (!rc) rc = ss_classes_flat_fold(g->fpt, g->pend_S, g->pend_fc, g->pend_base, g->zero32.p, s);
     for (uint32_t W = 2; W < 6 && !rc; ++W)
         if (g->pend_fc[W].table) rc = ss_counter_overflow(g->pend_fc[W].table, g->ovf.p + W, s);
-    if (!rc) rc = ss_check(hipMemcpyAsync(g->h_bad, g->ovf.p, 6 * 8, hipMemcpyDeviceToHost, s), "ingest overflow copy");
+    if (!rc) rc = ss_check(hipMemcpyAsync(g->hw.p->ovf, g->ovf.p, 6 * 8, hipMemcpyDeviceToHost, s), "ingest overflow copy");
     if (!rc) rc = ss_check(hipStreamSynchronize(s), "ingest deferred fold");
     if (rc) return rc;
     for (uint32_t W = 2; W < 6; ++W)
-        if (g->h_bad[W]) return fail_full(g, true);
+        if (g->hw.p->ovf[W]) return fail_full(g, true);
     return SS_OK;
 }
 
@@ -1257,17 +1205,18 @@ void spec_wait(ss_ingest* g) {
 // NB words, zeroed by the caller), every entry ranked into g->ordered by its first read, the ordered
 // entries' word offsets, the rows gathered into the pinned result buffer (ol).  sd null (the finish):
 // group q holds grs[q]->m entries, K in all.  sd = the speculative finish's device words: the counts stay
-// on the device (class W's at sd[W], their total at sd[6]); a group's capacity and K only bound them.
-int queue_order(ss_ingest* g, hipStream_t s, const std::vector<Group*>& grs, GDesc* h_desc, uint64_t* sd, uint64_t NB,
+// on the device (class W's at sd->cls[W], their total at sd->K); a group's capacity and K only bound them.
+int queue_order(ss_ingest* g, hipStream_t s, const std::vector<Group*>& grs, GDesc* h_desc, SpecWords* sd, uint64_t NB,
                 uint64_t K, const OutLayout& ol) {
     unsigned long long* bits = (unsigned long long*)g->slot.p;
     const GDesc* gd = g->gdesc.p;
-    const uint64_t* dK = sd ? sd + 6 : nullptr;
+    uint64_t* blksum = g->scan.p->blksum;
+    const uint64_t* dK = sd ? &sd->K : nullptr;
     const uint64_t empty_at = g->empty_count ? g->empty_first : kNoSlot;
     const uint64_t* none = nullptr;
     // a group's entry bound, and its entry count on the device (the host-sized grids cover m + 1 entries)
     auto bound = [&](const Group& gr) { return sd ? gr.cap + 1 : gr.m; };
-    auto count = [&](const Group& gr) { return sd ? (const uint64_t*)(sd + gr.W1 - 1) : none; };
+    auto count = [&](const Group& gr) { return sd ? (const uint64_t*)&sd->cls[gr.W1 - 1] : none; };
     for (size_t q = 0; q < grs.size(); ++q) {
         const Group& gr = *grs[q];
         hipLaunchKernelGGL(k_mark, dim3(grid_of(bound(gr) + (sd ? 0 : 1), 256)), dim3(256), 0, s, gr.first.p, bound(gr),
@@ -1275,7 +1224,7 @@ int queue_order(ss_ingest* g, hipStream_t s, const std::vector<Group*>& grs, GDe
         h_desc[q] = {gr.words.p, gr.counts.p, gr.W1, gr.L};
     }
     if (g->empty_count) hipLaunchKernelGGL(k_mark, dim3(1), dim3(256), 0, s, none, (uint64_t)0, none, empty_at, bits, none);
-    if (sd) hipLaunchKernelGGL(k_spec_total, dim3(1), dim3(64), 0, s, sd, g->empty_count ? 1ull : 0ull, none);
+    if (sd) hipLaunchKernelGGL(k_spec_total, dim3(1), dim3(64), 0, s, sd->cls, g->empty_count ? 1ull : 0ull, none);
     if (!grs.empty()) {
         const int rc = ss_check(hipMemcpyAsync(g->gdesc.p, h_desc, grs.size() * sizeof(GDesc), hipMemcpyHostToDevice, s),
                                 sd ? "spec desc" : "ingest desc");
@@ -1283,9 +1232,9 @@ int queue_order(ss_ingest* g, hipStream_t s, const std::vector<Group*>& grs, GDe
     }
     // marked reads before each read-map word (read order = dict order); woff holds that prefix first
     // (it becomes the word offsets below)
-    hipLaunchKernelGGL((k_scan_count<0>), dim3(kScanBlocks), dim3(256), 0, s, g->slot.p, NB, gd, g->scan.p, none);
-    hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(256), 0, s, g->scan.p);
-    hipLaunchKernelGGL((k_scan_apply<0>), dim3(kScanBlocks), dim3(256), 0, s, g->slot.p, NB, gd, g->scan.p, g->woff.p, none);
+    hipLaunchKernelGGL((k_scan_count<0>), dim3(kScanBlocks), dim3(256), 0, s, g->slot.p, NB, gd, blksum, none);
+    hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(256), 0, s, blksum);
+    hipLaunchKernelGGL((k_scan_apply<0>), dim3(kScanBlocks), dim3(256), 0, s, g->slot.p, NB, gd, blksum, g->woff.p, none);
     const uint64_t ocap = sd ? K : ~0ull;
     for (size_t q = 0; q < grs.size(); ++q) {
         const Group& gr = *grs[q];
@@ -1296,9 +1245,9 @@ int queue_order(ss_ingest* g, hipStream_t s, const std::vector<Group*>& grs, GDe
         hipLaunchKernelGGL(k_rank, dim3(1), dim3(256), 0, s, none, (uint64_t)0, none, 0u, empty_at, bits, g->woff.p,
                            g->ordered.p, none, ocap);
     // word offsets of the ordered entries (K on the device: past the bound the gather refuses)
-    hipLaunchKernelGGL((k_scan_count<1>), dim3(kScanBlocks), dim3(256), 0, s, g->ordered.p, K, gd, g->scan.p, dK);
-    hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(256), 0, s, g->scan.p);
-    hipLaunchKernelGGL((k_scan_apply<1>), dim3(kScanBlocks), dim3(256), 0, s, g->ordered.p, K, gd, g->scan.p, g->woff.p, dK);
+    hipLaunchKernelGGL((k_scan_count<1>), dim3(kScanBlocks), dim3(256), 0, s, g->ordered.p, K, gd, blksum, dK);
+    hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(256), 0, s, blksum);
+    hipLaunchKernelGGL((k_scan_apply<1>), dim3(kScanBlocks), dim3(256), 0, s, g->ordered.p, K, gd, blksum, g->woff.p, dK);
     // The speculative finish, up to a few million entries: the rows take about as long as the verify
     // beside them, so few waves, and the verify keeps the chip; past that the gather is the call's
     // bound and takes the full grid
@@ -1321,7 +1270,7 @@ int spec_launch(ss_ingest* g, const uint64_t* need, uint64_t N) {
     std::vector<Group*> cls;
     ss_flat_out fo[6] = {};
     uint64_t k_ub = 1, nw_ub = 0;
-    if ((rc = g->spec_dev.ensure(13))) return rc;
+    SpecWords* sd = g->spec_dev.p;
     for (auto& kv : g->groups) {
         Group& gr = kv.second;
         if (!gr.table || gr.L || gr.W1 - 1 >= 6 || g->pend_fc[gr.W1 - 1].table != gr.table) continue;
@@ -1329,7 +1278,7 @@ int spec_launch(ss_ingest* g, const uint64_t* need, uint64_t N) {
         const uint64_t cap = gr.cap + 1;
         if ((rc = gr.words.ensure(cap * gr.W1)) || (rc = gr.counts.ensure(cap)) || (rc = gr.first.ensure(cap)))
             return rc;
-        fo[W] = {gr.words.p, gr.counts.p, gr.first.p, g->spec_dev.p + W, g->spec_dev.p + 8, cap};
+        fo[W] = {gr.words.p, gr.counts.p, gr.first.p, &sd->cls[W], &sd->extract_ovf, cap};
         // (sizing mode 5, a test hook: the result bound taken as if the estimate were 0, so a chunk of
         // more than ~1024 distinct keys per class passes it and the finish runs the ordinary way)
         const uint64_t kb = std::min<uint64_t>(cap, (g->sizing == 5 ? 0 : need[W]) + 1024);
@@ -1341,21 +1290,19 @@ int spec_launch(ss_ingest* g, const uint64_t* need, uint64_t N) {
     const uint64_t NB = (N + 63) / 64;
     const uint64_t lb = (k_ub * 4 + 15) & ~15ull, out_bytes = lb + k_ub * 8 + nw_ub * 8 + 16;
     if ((rc = g->slot.ensure(NB)) || (rc = g->ordered.ensure(k_ub + 1)) || (rc = g->woff.ensure(std::max(k_ub, NB) + 1)) ||
-        (rc = g->gdesc.ensure(8)) || (rc = g->scan.ensure(kScanBlocks + 2 + 3 * (uint64_t)kLenBins + 8)) ||
-        (rc = g->out_host.ensure(out_bytes)))
+        (rc = g->gdesc.ensure(8)) || (rc = g->out_host.ensure(out_bytes)))
         return rc;
-    uint64_t* sd = g->spec_dev.p;
-    if ((rc = ss_check(hipMemsetAsync(sd, 0, 13 * 8, ss), "spec reset")) ||
+    if ((rc = ss_check(hipMemsetAsync(sd, 0, sizeof(SpecWords), ss), "spec reset")) ||
         (rc = ss_check(hipMemsetAsync(g->slot.p, 0, NB * 8, ss), "spec read map reset")))
         return rc;
     if ((rc = ss_classes_flat_extract(g->fpt, g->pend_S, g->pend_fc, g->pend_base, fo, g->zero32.p, ss))) return rc;
     g->wide = results_wide(g);
-    const OutLayout ol{g->out_host.p, g->out_host.cap, sd + 6, g->scan.p + kScanBlocks, 0, (unsigned long long*)(sd + 7),
+    const uint64_t* d_nw = &g->scan.p->total;     // (the word scan's, once queue_order has queued it)
+    const OutLayout ol{g->out_host.p, g->out_host.cap, &sd->K, d_nw, 0, (unsigned long long*)&sd->gather_bad,
                        g->compact, g->wide ? 1 : 0};
-    if ((rc = queue_order(g, ss, cls, g->h_gdesc, sd, NB, k_ub, ol))) return rc;
-    hipLaunchKernelGGL(k_spec_total, dim3(1), dim3(64), 0, ss, sd, g->empty_count ? 1ull : 0ull,
-                       (const uint64_t*)(g->scan.p + kScanBlocks), g->empty_count);
-    rc = ss_check(hipMemcpyAsync(g->h_spec, sd + 9, 4 * 8, hipMemcpyDeviceToHost, ss), "spec sizes");
+    if ((rc = queue_order(g, ss, cls, g->h_gdesc.p, sd, NB, k_ub, ol))) return rc;
+    hipLaunchKernelGGL(k_spec_total, dim3(1), dim3(64), 0, ss, sd->cls, g->empty_count ? 1ull : 0ull, d_nw, g->empty_count);
+    rc = ss_check(hipMemcpyAsync(g->h_spec.p, &sd->out, sizeof(SpecSizes), hipMemcpyDeviceToHost, ss), "spec sizes");
     if (!rc) rc = ss_check(hipEventRecord(g->ev_spec, ss), "spec event");
     if (!rc) rc = ss_check(hipGetLastError(), "spec finish");
     if (!rc) g->spec_inflight = true;
@@ -1457,7 +1404,7 @@ int split_chunk(ss_ingest* g, const Chunk& c, ChunkPlan& p) {
         hipLaunchKernelGGL(k_len_binscan, dim3(kLenBins), dim3(1024), 0, s, kSplitBlocks, g->blkhist.p, g->blkfirst.p,
                            g->split_out.p);
         hipLaunchKernelGGL(k_len_binstart, dim3(1), dim3(1024), 0, s, g->split_out.p);
-        if (!rc) rc = ss_check(hipMemcpyAsync(g->h_split, g->split_out.p, (3 * kLenBins + 1) * 8, hipMemcpyDeviceToHost, s),
+        if (!rc) rc = ss_check(hipMemcpyAsync(g->h_split.p, g->split_out.p, (3 * kLenBins + 1) * 8, hipMemcpyDeviceToHost, s),
                                "ingest split copy");
         if (!rc) rc = ss_check(hipEventRecord(g->ev_split, s), "ingest split event");
         // The previous chunks took the read-order path: its stride's row encode goes out now.  After two
@@ -1485,7 +1432,7 @@ int split_chunk(ss_ingest* g, const Chunk& c, ChunkPlan& p) {
             if (spec_enc && !p.spec_S) (void)hipStreamSynchronize(g->side[0]);   // (not joined) nothing left writing the buffers
             return rc;
         }
-        const uint64_t* hh = g->h_split;
+        const uint64_t* hh = g->h_split.p;
         if (p.spec_S && hh[3 * kLenBins] != p.spec_S) p.spec_S = 0;    // the queued encode did nothing (or is rewritten)
         Job shortj{kShortBin, 0, 0, kNoSlot};     // lengths 1..31: contiguous bins of the split, one job
         for (uint32_t b = 0; b < kLenBins; ++b) {
@@ -1599,13 +1546,13 @@ int encode_classes(ss_ingest* g, const Chunk& c, ChunkPlan& p) {
     // the registers come back (one sync): each class table is sized by its distinct keys so far
     // (the sketch covers every chunk of the call), not by its rows
     const uint64_t r0 = (uint64_t)p.wlo << kHllLog, nr = (uint64_t)(p.whi - p.wlo + 1) << kHllLog;
-    if (!rc) rc = ss_check(hipMemcpyAsync(g->h_hll + r0, g->hll.p + r0, nr * 4, hipMemcpyDeviceToHost, s), "ingest sketch copy");
+    if (!rc) rc = ss_check(hipMemcpyAsync(g->h_hll.p + r0, g->hll.p + r0, nr * 4, hipMemcpyDeviceToHost, s), "ingest sketch copy");
     if (!rc) rc = ss_check(hipStreamSynchronize(s), "ingest sketch");
     if (rc) return rc;
     for (const Job& jb : p.jobs) {
         if (jb.bin <= 32) continue;
         const uint32_t W = jb.bin - kClassBin0;
-        const double e = hll_estimate(g->h_hll + ((uint64_t)W << kHllLog));
+        const double e = hll_estimate(g->h_hll.p + ((uint64_t)W << kHllLog));
         p.need_cls[W] = g->sizing == 1 ? ~0ull                                   // the rows bound
                       : g->sizing == 2 ? (uint64_t)(e / 64.0) + 64                   // test: undersized
                                        : (uint64_t)(1.2 * e) + 256;                  // ~9 sigma above the estimate
@@ -1725,10 +1672,9 @@ int count_classes(ss_ingest* g, const Chunk& c, ChunkPlan& p) {
     // with the capacity) is replaced by a smaller one
     if (g->fpt && (ss_counter_capacity(g->fpt) < fcap || ss_counter_capacity(g->fpt) >= 8 * fcap)) {
         (void)hipStreamSynchronize(s);
-        ss_counter_destroy(g->fpt);
-        g->fpt = nullptr;
+        g->fpt.reset();      // (freed early: one of the wanted size takes its place)
     }
-    if (!g->fpt && (rc = ss_counter_create(fcap, &g->fpt))) return rc;
+    if (!g->fpt && (rc = ss_counter_create(fcap, g->fpt.put()))) return rc;
     // the scratch table's reset with the class tables' queued ones, one dispatch
     if ((rc = queue_reset(g, g->fpt)) || (rc = flush_prep(g)) || (rc = g->cls_flag.ensure(1))) return rc;
     // (sizing modes 3 / 4, test hooks: the flag starts raised, as if two keys shared a fingerprint;
@@ -1743,7 +1689,7 @@ int count_classes(ss_ingest* g, const Chunk& c, ChunkPlan& p) {
         // a first chunk of an add_device / add_blob also queues the speculative finish beside the verify
         const bool spec = c.spec_ok && c.base == 0 && g->bad_index == kNoSlot;
         rc = ss_classes_flat_verify(g->fpt, g->cls_words.p, p.w1max, c.n, g->cls_fps.p, g->cls_flag.p, s,
-                                    spec ? (void*)g->ev_reps : nullptr);
+                                    spec ? (void*)(hipEvent_t)g->ev_reps : nullptr);
         if (!rc) {      // pending once the flag comes back clear (checked after the chunk's sync)
             g->pend_S = p.w1max;
             g->pend_base = c.base;
@@ -1775,19 +1721,19 @@ int collect_chunk(ss_ingest* g, const Chunk& c, ChunkPlan& p) {
         g->nreads += c.n;
         return SS_OK;
     }
-    // (hb: the kLenBins + 1 first-bad words, then ho: the nj + 1 overflow words and the flag)
-    uint64_t* hb = g->h_bad;
-    uint64_t* ho = hb + kLenBins + 1;
-    int rc = ss_check(hipMemcpyAsync(hb, g->first_bad.p, (kLenBins + 1) * 8, hipMemcpyDeviceToHost, s), "ingest bad copy");
+    // (hb: the kLenBins + 1 first-bad words; ho: the nj + 1 overflow words -- a job is a bin or several)
+    HostWords& hw = *g->hw.p;
+    uint64_t *hb = hw.first_bad, *ho = hw.ovf;
+    int rc = ss_check(hipMemcpyAsync(hb, g->first_bad.p, sizeof(hw.first_bad), hipMemcpyDeviceToHost, s), "ingest bad copy");
     if (!rc) rc = ss_check(hipMemcpyAsync(ho, g->ovf.p, (nj + 1) * 8, hipMemcpyDeviceToHost, s), "ingest overflow copy");
     if (!rc && p.by_fp())
-        rc = ss_check(hipMemcpyAsync(ho + nj + 1, g->cls_flag.p, 4, hipMemcpyDeviceToHost, s), "ingest flag copy");
+        rc = ss_check(hipMemcpyAsync(&hw.fp_flag, g->cls_flag.p, 4, hipMemcpyDeviceToHost, s), "ingest flag copy");
     if (!rc) rc = ss_check(hipStreamSynchronize(s), "ingest chunk");
     if (rc) return rc;
     for (size_t j = 0; j <= nj; ++j)
         if (ho[j] && (j < nj || p.by_fp())) return fail_full(g, true);
-    g->pend = p.pend_now && !(uint32_t)ho[nj + 1];
-    if (p.by_fp() && (uint32_t)ho[nj + 1]) {
+    g->pend = p.pend_now && !hw.fp_flag;
+    if (p.by_fp() && hw.fp_flag) {
         spec_wait(g);                  // (it reads the class tables the exact path now fills)
         // two keys share a fingerprint: the class tables were left untouched, count them exactly
         if (p.flat) {   // class-ordered rows and their row maps first (the one-pass class encode)
@@ -1881,10 +1827,8 @@ int process_chunk(ss_ingest* g, Chunk c) {
 // their (empty) tables -- the finish; export and merge flush the scratch into the tables first.
 int extract_groups(ss_ingest* g, std::vector<Group*>& placed, bool flat = false) {
     hipStream_t s = g->stream;
-    int rc = g->scan.ensure(kScanBlocks + 2 + 3 * (uint64_t)kLenBins + 8);
-    if (rc) return rc;
-    uint64_t* d_cnt = g->scan.p + kScanBlocks + 2;
-    rc = ss_check(hipMemsetAsync(d_cnt, 0, 3 * (uint64_t)kLenBins * 8, s), "ingest word totals reset");
+    ExtractCount* d_cnt = g->dw.p->extract;
+    int rc = ss_check(hipMemsetAsync(d_cnt, 0, sizeof(g->dw.p->extract), s), "ingest word totals reset");
     if (rc) return rc;
     ss_flat_out fo[6] = {};
     bool any_flat = false;
@@ -1900,30 +1844,30 @@ int extract_groups(ss_ingest* g, std::vector<Group*>& placed, bool flat = false)
             return rc;
         if (flat && !gr.L && W - 1 < 6 && g->pend_fc[W - 1].table == gr.table) {
             // at most cap entries (the extract raises the overflow word past it, as the fold would)
-            fo[W - 1] = {gr.words.p, gr.counts.p, gr.first.p, d_cnt + 3 * q, d_cnt + 3 * q + 1, cap};
+            fo[W - 1] = {gr.words.p, gr.counts.p, gr.first.p, &d_cnt[q].count, &d_cnt[q].overflow, cap};
             any_flat = true;
             placed.push_back(&gr);
             continue;
         }
         rc = ss_counter_extract_words(gr.table, 1, gr.fps.p, gr.lens.p, gr.words.p, gr.counts.p, gr.first.p, cap,
-                                      d_cnt + 3 * q, s);
-        if (!rc) rc = ss_counter_overflow(gr.table, d_cnt + 3 * q + 1, s);
+                                      &d_cnt[q].count, s);
+        if (!rc) rc = ss_counter_overflow(gr.table, &d_cnt[q].overflow, s);
         if (rc) return rc;
         if (gr.acc_rows)    // the counts spilled out of the table (u64) back onto its entries
             hipLaunchKernelGGL(k_add_acc, dim3(grid_of(cap, 256)), dim3(256), 0, s, gr.counts.p, gr.first.p,
-                               (const uint64_t*)(d_cnt + 3 * q), gr.acc.p, gr.acc_rows);
+                               (const uint64_t*)&d_cnt[q].count, gr.acc.p, gr.acc_rows);
         placed.push_back(&gr);
     }
     if (any_flat && (rc = ss_classes_flat_extract(g->fpt, g->pend_S, g->pend_fc, g->pend_base, fo, g->zero32.p, s)))
         return rc;
     if (!placed.empty()) {
-        rc = ss_check(hipMemcpyAsync(g->h_bad, d_cnt, 3 * placed.size() * 8, hipMemcpyDeviceToHost, s), "ingest");
+        rc = ss_check(hipMemcpyAsync(g->hw.p->extract, d_cnt, placed.size() * sizeof(ExtractCount), hipMemcpyDeviceToHost, s), "ingest");
         if (!rc) rc = ss_check(hipStreamSynchronize(s), "ingest extract");
         if (rc) return rc;
     }
     for (size_t q = 0; q < placed.size(); ++q) {
-        if (g->h_bad[3 * q + 1]) return ss_fail(SS_EFULL, "ingest: a length's counter table overflowed");
-        placed[q]->m = g->h_bad[3 * q];
+        if (g->hw.p->extract[q].overflow) return ss_fail(SS_EFULL, "ingest: a length's counter table overflowed");
+        placed[q]->m = g->hw.p->extract[q].count;
         // a class table keys W = W1 - 1 words for every entry (its lengths are 32(W-1)+1 .. 32W)
         placed[q]->nw = placed[q]->L ? placed[q]->m : placed[q]->m * (placed[q]->W1 - 1);
     }
@@ -1946,12 +1890,13 @@ int index_chunk(ss_ingest* g, const uint8_t* d_buf, uint64_t use, uint64_t line0
             return rc;
         rc = ss_fastq_index_onepass(d_buf, use, line0, at_eof ? 1 : 0, fq.ws.p, wsb, g->offs.p, g->dlens.p, fq.aux.p,
                                     maxr, fq.counts.p, s);
-        if (!rc) rc = ss_check(hipMemcpyAsync(g->h_bad, fq.counts.p, 24, hipMemcpyDeviceToHost, s), "ingest fq");
+        uint64_t* hc = g->hw.p->fq_counts;      // newlines, records, overflow
+        if (!rc) rc = ss_check(hipMemcpyAsync(hc, fq.counts.p, sizeof(g->hw.p->fq_counts), hipMemcpyDeviceToHost, s), "ingest fq");
         if (!rc) rc = ss_check(hipStreamSynchronize(s), "ingest fq");
         if (rc) return rc;
-        *nl = g->h_bad[0];
-        *nrec = g->h_bad[1];
-        if (g->h_bad[2]) maxr *= 2;
+        *nl = hc[0];
+        *nrec = hc[1];
+        if (hc[2]) maxr *= 2;
         else if (*nrec <= maxr) return SS_OK;
         else maxr = *nrec;
     }
@@ -1985,30 +1930,25 @@ int ss_ingest_create(int device, ss_ingest** h_out) {
     if (rc) return rc;
     ss_ingest* g = new ss_ingest();
     g->device = device;
-    rc = ss_check(hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking), "ingest stream");
+    auto event = [](Event& e) { return ss_check(hipEventCreateWithFlags(e.put(), hipEventDisableTiming), "ingest event"); };
+    rc = ss_check(hipStreamCreateWithFlags(g->stream.put(), hipStreamNonBlocking), "ingest stream");
     for (int k = 0; k < ss_ingest::kSide && !rc; ++k) {
-        rc = ss_check(hipStreamCreateWithFlags(&g->side[k], hipStreamNonBlocking), "ingest side stream");
-        if (!rc) rc = ss_check(hipEventCreateWithFlags(&g->ev_join[k], hipEventDisableTiming), "ingest event");
+        rc = ss_check(hipStreamCreateWithFlags(g->side[k].put(), hipStreamNonBlocking), "ingest side stream");
+        if (!rc) rc = event(g->ev_join[k]);
     }
-    if (!rc) rc = ss_check(hipEventCreateWithFlags(&g->ev_fork, hipEventDisableTiming), "ingest event");
-    if (!rc) rc = ss_check(hipHostMalloc((void**)&g->h_split, (3 * kLenBins + 1) * 8, hipHostMallocDefault), "ingest pinned");
-    if (!rc) rc = ss_check(hipHostMalloc((void**)&g->h_bad, (3 * kLenBins + 8) * 8, hipHostMallocDefault), "ingest pinned");
-    if (!rc) rc = ss_check(hipHostMalloc((void**)&g->h_hll, (33ull << kHllLog) * 4, hipHostMallocDefault), "ingest pinned");
-    if (!rc) rc = g->hll.ensure(33ull << kHllLog);
-    if (!rc) rc = ss_check(hipMemsetAsync(g->hll.p, 0, (33ull << kHllLog) * 4, g->stream), "ingest sketch reset");
     if (!rc) {       // the speculative finish runs beside the verify: it gets the CU slots first
         int lo = 0, hi = 0;
         (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
-        rc = ss_check(hipStreamCreateWithPriority(&g->spec_stream, hipStreamNonBlocking, hi), "ingest spec stream");
+        rc = ss_check(hipStreamCreateWithPriority(g->spec_stream.put(), hipStreamNonBlocking, hi), "ingest spec stream");
     }
-    if (!rc) rc = ss_check(hipEventCreateWithFlags(&g->ev_reps, hipEventDisableTiming), "ingest event");
-    if (!rc) rc = ss_check(hipEventCreateWithFlags(&g->ev_split, hipEventDisableTiming), "ingest event");
-    if (!rc) rc = ss_check(hipEventCreateWithFlags(&g->ev_spec, hipEventDisableTiming), "ingest event");
-    if (!rc) rc = ss_check(hipHostMalloc((void**)&g->h_spec, 4 * 8, hipHostMallocDefault), "ingest pinned");
-    if (!rc) rc = ss_check(hipHostMalloc((void**)&g->h_gdesc, 8 * sizeof(GDesc), hipHostMallocDefault), "ingest pinned");
-    if (!rc) rc = g->zero32.ensure(1);
-    if (!rc) rc = ss_check(hipMemsetAsync(g->zero32.p, 0, 4, g->stream), "ingest zero word");
-    if (rc) {
+    // the events, the buffers whose size never changes, the words that start at 0
+    if (rc || (rc = event(g->ev_fork)) || (rc = event(g->ev_reps)) || (rc = event(g->ev_split)) || (rc = event(g->ev_spec)) ||
+        (rc = g->h_split.ensure(3 * kLenBins + 1)) || (rc = g->hw.ensure(1)) || (rc = g->dw.ensure(1)) ||
+        (rc = g->scan.ensure(1)) || (rc = g->spec_dev.ensure(1)) || (rc = g->h_spec.ensure(1)) ||
+        (rc = g->h_gdesc.ensure(8)) || (rc = g->h_hll.ensure(33ull << kHllLog)) || (rc = g->hll.ensure(33ull << kHllLog)) ||
+        (rc = g->zero32.ensure(1)) ||
+        (rc = ss_check(hipMemsetAsync(g->hll.p, 0, (33ull << kHllLog) * 4, g->stream), "ingest sketch reset")) ||
+        (rc = ss_check(hipMemsetAsync(g->zero32.p, 0, 4, g->stream), "ingest zero word"))) {
         ss_ingest_destroy(g);
         return rc;
     }
@@ -2023,12 +1963,9 @@ int ss_ingest_reset(ss_ingest* g) {
     // tables go back to the pool; a length's row map and extraction buffers stay (grow-only) for the
     // next call (a fresh hipMalloc per call and length costs more than the counting)
     for (auto& kv : g->groups) {
-        table_put(g, kv.second.table);
-        kv.second.table = nullptr;
-        kv.second.cap = 0;
-        kv.second.rows = 0;
-        kv.second.m = 0;
-        kv.second.acc_rows = 0;
+        Group& gr = kv.second;
+        table_put(g, std::move(gr.table));
+        gr.cap = gr.rows = gr.m = gr.acc_rows = 0;
     }
     g->nreads = 0;
     g->since_spill = 0;
@@ -2042,7 +1979,6 @@ int ss_ingest_reset(ss_ingest* g) {
     g->failed = false;
     g->exported = false;
     g->pend = false;
-    if (!g->hll.p) return SS_OK;
     return ss_check(hipMemsetAsync(g->hll.p, 0, (33ull << kHllLog) * 4, g->stream), "ingest sketch reset");
 }
 
@@ -2080,43 +2016,14 @@ int ss_ingest_set_adapter(ss_ingest* g, const uint8_t* h_adapter, uint32_t A, ui
 
 int ss_ingest_destroy(ss_ingest* g) {
     if (!g) return SS_OK;
-    ss_ingest_reset(g);
-    for (auto& kv : g->groups) {
-        kv.second.rowmap.release();
-        kv.second.fps.release(), kv.second.words.release(), kv.second.counts.release(), kv.second.first.release();
-        kv.second.lens.release(), kv.second.xread.release();
-    }
-    g->groups.clear();
-    for (auto& p : g->pool) ss_counter_destroy(p.second);
-    g->pool.clear();
-    g->fq.release();
-    g->stage.release();
-    g->out_host.release();
-    g->dbuf.release(), g->offs.release(), g->dlens.release(), g->order.release(), g->blkhist.release();
-    g->blkfirst.release(), g->split_out.release(), g->rows.release(), g->first_bad.release();
-    g->slot.release(), g->ordered.release(), g->woff.release(), g->scan.release(), g->gdesc.release();
-    g->cls_words.release(), g->cls_fps.release(), g->hll.release(), g->ovf.release();
-    g->cls_flag.release(), g->zero32.release();
-    if (g->fpt) ss_counter_destroy(g->fpt);
-    g->fpt = nullptr;
-    g->mg_words.release(), g->mg_counts.release(), g->mg_first.release(), g->mg_lens.release(), g->mg_take.release();
-    if (g->h_hll) (void)hipHostFree(g->h_hll);
-    if (g->h_split) (void)hipHostFree(g->h_split);
-    if (g->h_bad) (void)hipHostFree(g->h_bad);
-    if (g->h_spec) (void)hipHostFree(g->h_spec);
-    if (g->h_gdesc) (void)hipHostFree(g->h_gdesc);
-    g->spec_dev.release();
-    if (g->ev_reps) (void)hipEventDestroy(g->ev_reps);
-    if (g->ev_split) (void)hipEventDestroy(g->ev_split);
-    if (g->ev_spec) (void)hipEventDestroy(g->ev_spec);
-    if (g->spec_stream) (void)hipStreamDestroy(g->spec_stream);
-    for (int k = 0; k < ss_ingest::kSide; ++k) {
-        if (g->side[k]) (void)hipStreamDestroy(g->side[k]);
-        if (g->ev_join[k]) (void)hipEventDestroy(g->ev_join[k]);
-    }
-    if (g->ev_fork) (void)hipEventDestroy(g->ev_fork);
-    if (g->stream) (void)hipStreamDestroy(g->stream);
-    delete g;
+    (void)hipSetDevice(g->device);
+    spec_wait(g);
+    auto wait = [](const Stream& s) {
+        if (s) (void)hipStreamSynchronize(s);
+    };
+    wait(g->stream), wait(g->spec_stream), wait(g->fq.copy);
+    for (const Stream& s : g->side) wait(s);
+    delete g;       // (nothing queued is left to read what the members free: buffers first, streams last)
     return SS_OK;
 }
 
@@ -2330,9 +2237,9 @@ static int finish_impl(ss_ingest* g, uint64_t* h_nkeys, uint64_t* h_nwords) {
         const int e = ss_check(hipEventSynchronize(g->ev_spec), "ingest spec finish");
         g->spec_inflight = false;
         if (e) return e;
-        if (!g->h_spec[2]) {        // (stays valid: a second finish returns the same rows)
-            g->nkeys = g->h_spec[0];
-            g->nwords = g->h_spec[1];
+        if (!g->h_spec.p->bad) {    // (stays valid: a second finish returns the same rows)
+            g->nkeys = g->h_spec.p->K;
+            g->nwords = g->h_spec.p->NW;
             *h_nkeys = g->nkeys;
             *h_nwords = g->nwords;
             return SS_OK;
@@ -2356,8 +2263,7 @@ static int finish_impl(ss_ingest* g, uint64_t* h_nkeys, uint64_t* h_nwords) {
     uint64_t co = 0, wo0 = 0;
     results_layout(K, 0, 8, co, wo0);      // (the plain layout bounds the compact one)
     if ((rc = g->gdesc.ensure(placed.size() + 1)) || (rc = g->ordered.ensure(K + 1)) ||
-        (rc = g->woff.ensure(std::max(K, NB) + 1)) || (rc = g->out_host.ensure(wo0 + NW * 8 + 16)) ||
-        (rc = g->spec_dev.ensure(13)))
+        (rc = g->woff.ensure(std::max(K, NB) + 1)) || (rc = g->out_host.ensure(wo0 + NW * 8 + 16)))
         return rc;
     std::vector<GDesc> desc(placed.size());
     g->wide = results_wide(g);
@@ -2399,10 +2305,10 @@ int ss_ingest_export(ss_ingest* g, uint64_t* h_nkeys) {
             hipLaunchKernelGGL(k_count_max, dim3(std::min<unsigned>(grid_of(gr->m, 256), kCountMaxBlocks)), dim3(256), 0,
                                g->stream, gr->counts.p, gr->m,
                                (unsigned long long*)g->mg_take.p);
-    rc = ss_check(hipMemcpyAsync(g->h_bad + 3 * kLenBins + 4, g->mg_take.p, 8, hipMemcpyDeviceToHost, g->stream), "ingest export max");
+    rc = ss_check(hipMemcpyAsync(&g->hw.p->export_max, g->mg_take.p, 8, hipMemcpyDeviceToHost, g->stream), "ingest export max");
     if (!rc) rc = ss_check(hipStreamSynchronize(g->stream), "ingest export");
     if (rc) return rc;
-    g->xmax = g->h_bad[3 * kLenBins + 4];
+    g->xmax = g->hw.p->export_max;
     g->exported = true;
     if (h_nkeys) *h_nkeys = keys + (g->empty_count ? 1 : 0);
     return SS_OK;
@@ -2512,8 +2418,7 @@ int ss_ingest_merge(ss_ingest* dst, ss_ingest* src, uint64_t src_base) {
                                    m, room);
                 cnt = dst->mg_take.p;
             }
-            rc = gr.W1 == 1 ? ss_counter_merge(gr.table, dst->mg_words.p, dst->mg_lens.p, cnt, dst->mg_first.p, m, s)
-                            : ss_counter_merge_words(gr.table, dst->mg_words.p, cnt, dst->mg_first.p, m, s);
+            rc = table_merge(gr.table, gr.W1, dst->mg_words.p, dst->mg_lens.p, cnt, dst->mg_first.p, m, s);
             if (rc) break;
             left = left > room ? left - room : 0;
             if (left) {

@@ -5,6 +5,8 @@
 
 #include <vector>
 
+#include "ss_owned.h"
+
 // The CPUs of `device`'s NUMA node (sysfs, by PCI bus id) that this process's affinity mask allows;
 // *node = that node (-1: unknown), *allowed = the mask's CPU count.  Empty when the node is unknown
 // or the intersection is empty (ss_stage.hip: the stager's copy threads, the FASTQ reader ring).
@@ -13,6 +15,38 @@ std::vector<int> ss_gpu_numa_cpus(int device, int* node, int* allowed);
 int ss_fail(int code, const char* msg);
 // SS_OK if e == hipSuccess, otherwise record "<what>: <hip error string>" and return SS_EHIP.
 int ss_check(hipError_t e, const char* what);
+
+// The HIP side of ss_owned.h: device memory, pinned host memory, streams and events that free themselves.
+struct DevMem {
+    static int alloc(void** p, uint64_t bytes) {
+        if (hipMalloc(p, bytes) == hipSuccess) return SS_OK;
+        (void)hipGetLastError();
+        return ss_fail(SS_ENOMEM, "out of device memory");
+    }
+    static void free(void* p) { (void)hipFree(p); }
+    static int copy_keep(void* dst, const void* src, uint64_t bytes, void* stream) {
+        hipStream_t s = (hipStream_t)stream;
+        const int rc = bytes ? ss_check(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, s), "grow copy") : SS_OK;
+        return rc ? rc : ss_check(hipStreamSynchronize(s), "grow copy");
+    }
+    static void before_regrow() { (void)hipDeviceSynchronize(); }
+};
+struct PinMem {
+    static int alloc(void** p, uint64_t bytes) {
+        if (hipHostMalloc(p, bytes, hipHostMallocDefault) == hipSuccess) return SS_OK;
+        (void)hipGetLastError();
+        return ss_fail(SS_ENOMEM, "out of pinned host memory");
+    }
+    static void free(void* p) { (void)hipHostFree(p); }
+    static void before_regrow() {}       // (no ensure_keep: nothing here grows a pinned buffer in place)
+};
+template <typename T>
+using DBuf = Buf<T, DevMem, 1024>;              // grow-only device buffer
+using HBuf = Buf<uint8_t, PinMem, 1 << 20>;     // grow-only pinned host buffer
+template <typename T>
+using Pinned = Buf<T, PinMem>;                  // a pinned array (or one struct) of a fixed size
+using Stream = Handle<hipStream_t, hipStreamDestroy>;
+using Event = Handle<hipEvent_t, hipEventDestroy>;
 // Launch-side entry shared by ss_encode_fixed / ss_encode_hamming_ref.
 extern "C" int ss_encode_fixed_impl(const uint8_t* d_ascii, uint64_t n, uint32_t L, uint64_t stride,
                                     uint64_t* d_words, uint32_t wpr, uint64_t* d_first_bad,

@@ -24,6 +24,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <memory>
 #include <new>
 #include <vector>
 
@@ -33,16 +34,12 @@
 namespace {
 
 struct Slot {
-    uint8_t* h_in = nullptr;    // pinned staging (pageable user input)
-    uint8_t* h_out = nullptr;   // pinned staging (pageable user output)
-    uint8_t* h_out2 = nullptr;
-    uint8_t* d_in = nullptr;
-    uint8_t* d_out = nullptr;
-    uint8_t* d_out2 = nullptr;
-    uint64_t* d_fb = nullptr;   // the chunk's first-bad read (chunk-relative)
-    uint64_t* h_fb = nullptr;   // pinned copy of it
-    hipEvent_t ev_in = nullptr, ev_k = nullptr, ev_out = nullptr;
-    hipEvent_t ev_h0 = nullptr, ev_k0 = nullptr, ev_o0 = nullptr;   // stage starts (ss_stager_set_timing)
+    Pinned<uint8_t> h_in, h_out, h_out2;   // pinned staging (pageable user input / outputs)
+    Buf<uint8_t, DevMem> d_in, d_out, d_out2;
+    Buf<uint64_t, DevMem> d_fb; // the chunk's first-bad read (chunk-relative)
+    Pinned<uint64_t> h_fb;      // pinned copy of it
+    Event ev_in, ev_k, ev_out;
+    Event ev_h0, ev_k0, ev_o0;  // stage starts (ss_stager_set_timing)
     bool busy = false, timed = false;
     uint64_t base = 0, m = 0;
 };
@@ -79,10 +76,9 @@ bool is_pinned(const void* p) {
 struct ss_stager {
     int device = 0;
     uint64_t chunk_bytes = 0;
+    Stream s_in, s_k, s_out;    // (before the slots: their buffers are freed first, the streams last)
     std::vector<Slot> slots;
-    hipStream_t s_in = nullptr, s_k = nullptr, s_out = nullptr;
-    CopyPool* pool = nullptr;
-    bool out2_ready = false;
+    std::unique_ptr<CopyPool> pool;
     // placement: copy threads, CPUs in the process's affinity mask, the GPU's NUMA
     // node (-1: unknown), CPUs the copy threads were pinned to (the node's CPUs in the mask; 0: none)
     int copy_threads = 0, affinity_cpus = 0, numa_node = -1, pinned_cpus = 0;
@@ -99,40 +95,17 @@ namespace {
 void free_stager(ss_stager* st) {
     if (!st) return;
     (void)hipSetDevice(st->device);
-    if (st->s_in) (void)hipStreamSynchronize(st->s_in);
-    if (st->s_k) (void)hipStreamSynchronize(st->s_k);
-    if (st->s_out) (void)hipStreamSynchronize(st->s_out);
-    for (Slot& s : st->slots) {
-        if (s.h_in) (void)hipHostFree(s.h_in);
-        if (s.h_out) (void)hipHostFree(s.h_out);
-        if (s.h_out2) (void)hipHostFree(s.h_out2);
-        if (s.h_fb) (void)hipHostFree(s.h_fb);
-        if (s.d_in) (void)hipFree(s.d_in);
-        if (s.d_out) (void)hipFree(s.d_out);
-        if (s.d_out2) (void)hipFree(s.d_out2);
-        if (s.d_fb) (void)hipFree(s.d_fb);
-        if (s.ev_in) (void)hipEventDestroy(s.ev_in);
-        if (s.ev_k) (void)hipEventDestroy(s.ev_k);
-        if (s.ev_out) (void)hipEventDestroy(s.ev_out);
-        if (s.ev_h0) (void)hipEventDestroy(s.ev_h0);
-        if (s.ev_k0) (void)hipEventDestroy(s.ev_k0);
-        if (s.ev_o0) (void)hipEventDestroy(s.ev_o0);
-    }
-    if (st->s_in) (void)hipStreamDestroy(st->s_in);
-    if (st->s_k) (void)hipStreamDestroy(st->s_k);
-    if (st->s_out) (void)hipStreamDestroy(st->s_out);
-    delete st->pool;
-    delete st;
+    for (const Stream* s : {&st->s_in, &st->s_k, &st->s_out})
+        if (*s) (void)hipStreamSynchronize(*s);
+    delete st;      // (the slots' buffers and events, then the streams)
 }
 
 int ensure_out2(ss_stager* st) {
-    if (st->out2_ready) return SS_OK;
-    for (Slot& s : st->slots) {
-        int rc = ss_check(hipHostMalloc((void**)&s.h_out2, st->chunk_bytes, hipHostMallocDefault), "hipHostMalloc");
-        if (!rc) rc = ss_check(hipMalloc((void**)&s.d_out2, st->chunk_bytes), "hipMalloc");
+    for (Slot& s : st->slots) {     // (nothing to do once they are there; after a failure half-way, the rest)
+        int rc = s.h_out2.ensure(st->chunk_bytes);
+        if (!rc) rc = s.d_out2.ensure(st->chunk_bytes);
         if (rc) return rc;
     }
-    st->out2_ready = true;
     return SS_OK;
 }
 
@@ -160,10 +133,10 @@ int drain(ss_stager* st, Slot& s, const HostOp& op, bool out_pinned, bool out2_p
         s.timed = false;
     }
     t0 = Clock::now();
-    if (!out_pinned) st->pool->copy(op.h_out + s.base * op.out_bpr, s.h_out, s.m * op.out_bpr);
-    if (op.h_out2 && !out2_pinned) st->pool->copy(op.h_out2 + s.base * op.out2_bpr, s.h_out2, s.m * op.out2_bpr);
+    if (!out_pinned) st->pool->copy(op.h_out + s.base * op.out_bpr, s.h_out.p, s.m * op.out_bpr);
+    if (op.h_out2 && !out2_pinned) st->pool->copy(op.h_out2 + s.base * op.out2_bpr, s.h_out2.p, s.m * op.out2_bpr);
     st->ms[1] += ms_since(t0);
-    if (op.has_fb && *s.h_fb != ~0ull && *first_bad == ~0ull) *first_bad = s.base + *s.h_fb;
+    if (op.has_fb && *s.h_fb.p != ~0ull && *first_bad == ~0ull) *first_bad = s.base + *s.h_fb.p;
     return SS_OK;
 }
 
@@ -193,30 +166,30 @@ int run(ss_stager* st, const HostOp& op, uint64_t n, uint64_t* h_first_bad) {
         const size_t in_b = s.m * op.in_bpr;
         if (!in_pinned) {
             const auto t0 = Clock::now();
-            st->pool->copy(s.h_in, src, in_b);
+            st->pool->copy(s.h_in.p, src, in_b);
             st->ms[0] += ms_since(t0);
-            src = s.h_in;
+            src = s.h_in.p;
         }
         s.timed = st->timing && s.ev_h0;
         if (s.timed) rc = ss_check(hipEventRecord(s.ev_h0, st->s_in), "hipEventRecord");
-        if (!rc) rc = ss_check(hipMemcpyAsync(s.d_in, src, in_b, hipMemcpyHostToDevice, st->s_in), "H2D");
+        if (!rc) rc = ss_check(hipMemcpyAsync(s.d_in.p, src, in_b, hipMemcpyHostToDevice, st->s_in), "H2D");
         if (!rc) rc = ss_check(hipEventRecord(s.ev_in, st->s_in), "hipEventRecord");
         if (!rc) rc = ss_check(hipStreamWaitEvent(st->s_k, s.ev_in, 0), "hipStreamWaitEvent");
         if (!rc && s.timed) rc = ss_check(hipEventRecord(s.ev_k0, st->s_k), "hipEventRecord");
-        if (!rc) rc = op.launch(op, s.d_in, s.m, s.d_out, s.d_out2, s.d_fb, st->s_k);
+        if (!rc) rc = op.launch(op, s.d_in.p, s.m, s.d_out.p, s.d_out2.p, s.d_fb.p, st->s_k);
         if (!rc) rc = ss_check(hipEventRecord(s.ev_k, st->s_k), "hipEventRecord");
         if (!rc) rc = ss_check(hipStreamWaitEvent(st->s_out, s.ev_k, 0), "hipStreamWaitEvent");
         if (!rc && s.timed) rc = ss_check(hipEventRecord(s.ev_o0, st->s_out), "hipEventRecord");
         if (!rc) {
-            uint8_t* dst = out_pinned ? op.h_out + s.base * op.out_bpr : s.h_out;
-            rc = ss_check(hipMemcpyAsync(dst, s.d_out, s.m * op.out_bpr, hipMemcpyDeviceToHost, st->s_out), "D2H");
+            uint8_t* dst = out_pinned ? op.h_out + s.base * op.out_bpr : s.h_out.p;
+            rc = ss_check(hipMemcpyAsync(dst, s.d_out.p, s.m * op.out_bpr, hipMemcpyDeviceToHost, st->s_out), "D2H");
         }
         if (!rc && op.h_out2) {
-            uint8_t* dst = out2_pinned ? op.h_out2 + s.base * op.out2_bpr : s.h_out2;
-            rc = ss_check(hipMemcpyAsync(dst, s.d_out2, s.m * op.out2_bpr, hipMemcpyDeviceToHost, st->s_out), "D2H");
+            uint8_t* dst = out2_pinned ? op.h_out2 + s.base * op.out2_bpr : s.h_out2.p;
+            rc = ss_check(hipMemcpyAsync(dst, s.d_out2.p, s.m * op.out2_bpr, hipMemcpyDeviceToHost, st->s_out), "D2H");
         }
         if (!rc && op.has_fb)
-            rc = ss_check(hipMemcpyAsync(s.h_fb, s.d_fb, sizeof(uint64_t), hipMemcpyDeviceToHost, st->s_out), "D2H");
+            rc = ss_check(hipMemcpyAsync(s.h_fb.p, s.d_fb.p, sizeof(uint64_t), hipMemcpyDeviceToHost, st->s_out), "D2H");
         if (!rc) rc = ss_check(hipEventRecord(s.ev_out, st->s_out), "hipEventRecord");
         s.busy = true;
     }
@@ -321,9 +294,8 @@ int ss_stager_set_timing(ss_stager* st, int on) {
     int rc = ss_check(hipSetDevice(st->device), "hipSetDevice");
     for (Slot& s : st->slots) {
         if (rc || !on || s.ev_h0) break;
-        rc = ss_check(hipEventCreate(&s.ev_h0), "hipEventCreate");
-        if (!rc) rc = ss_check(hipEventCreate(&s.ev_k0), "hipEventCreate");
-        if (!rc) rc = ss_check(hipEventCreate(&s.ev_o0), "hipEventCreate");
+        for (Event* e : {&s.ev_h0, &s.ev_k0, &s.ev_o0})
+            if (!rc) rc = ss_check(hipEventCreate(e->put()), "hipEventCreate");
     }
     if (rc) return rc;
     st->timing = on != 0;
@@ -358,22 +330,17 @@ int ss_stager_create(int device, uint64_t chunk_bytes, uint32_t nslots, uint32_t
     st->device = device;
     st->chunk_bytes = chunk_bytes;
     int rc = ss_check(hipSetDevice(device), "hipSetDevice");
-    if (!rc) rc = ss_check(hipStreamCreateWithFlags(&st->s_in, hipStreamNonBlocking), "hipStreamCreate");
-    if (!rc) rc = ss_check(hipStreamCreateWithFlags(&st->s_k, hipStreamNonBlocking), "hipStreamCreate");
-    if (!rc) rc = ss_check(hipStreamCreateWithFlags(&st->s_out, hipStreamNonBlocking), "hipStreamCreate");
+    for (Stream* s : {&st->s_in, &st->s_k, &st->s_out})
+        if (!rc) rc = ss_check(hipStreamCreateWithFlags(s->put(), hipStreamNonBlocking), "hipStreamCreate");
     st->slots.resize(nslots);
     for (uint32_t i = 0; i < nslots && !rc; ++i) {
         Slot& s = st->slots[i];
-        rc = ss_check(hipHostMalloc((void**)&s.h_in, chunk_bytes, hipHostMallocDefault), "hipHostMalloc");
-        if (!rc) rc = ss_check(hipHostMalloc((void**)&s.h_out, chunk_bytes, hipHostMallocDefault), "hipHostMalloc");
-        if (!rc) rc = ss_check(hipHostMalloc((void**)&s.h_fb, sizeof(uint64_t), hipHostMallocDefault), "hipHostMalloc");
-        if (!rc) rc = ss_check(hipMalloc((void**)&s.d_in, chunk_bytes), "hipMalloc");
-        if (!rc) rc = ss_check(hipMalloc((void**)&s.d_out, chunk_bytes), "hipMalloc");
-        if (!rc) rc = ss_check(hipMalloc((void**)&s.d_fb, sizeof(uint64_t)), "hipMalloc");
+        if ((rc = s.h_in.ensure(chunk_bytes)) || (rc = s.h_out.ensure(chunk_bytes)) || (rc = s.h_fb.ensure(1)) ||
+            (rc = s.d_in.ensure(chunk_bytes)) || (rc = s.d_out.ensure(chunk_bytes)) || (rc = s.d_fb.ensure(1)))
+            break;
         // (timing-capable: they also end the stage spans of ss_stager_set_timing)
-        if (!rc) rc = ss_check(hipEventCreate(&s.ev_in), "hipEventCreate");
-        if (!rc) rc = ss_check(hipEventCreate(&s.ev_k), "hipEventCreate");
-        if (!rc) rc = ss_check(hipEventCreate(&s.ev_out), "hipEventCreate");
+        for (Event* e : {&s.ev_in, &s.ev_k, &s.ev_out})
+            if (!rc) rc = ss_check(hipEventCreate(e->put()), "hipEventCreate");
     }
     if (rc) {
         free_stager(st);
@@ -382,7 +349,7 @@ int ss_stager_create(int device, uint64_t chunk_bytes, uint32_t nslots, uint32_t
     st->copy_threads = (int)copy_threads;
     const std::vector<int> cpus = placement(st);
     try {
-        st->pool = new CopyPool((int)copy_threads, cpus);     // (host_threads.h)
+        st->pool.reset(new CopyPool((int)copy_threads, cpus));     // (host_threads.h)
     } catch (...) {     // no memory, or a worker thread that could not start
     }
     if (!st->pool) {

@@ -474,6 +474,34 @@ def test_device_ingest_count_spill_merge(gpu, oracle, lo, hi):
     assert np.array_equal(gw, ew)
 
 
+def test_device_ingest_destroy_frees_spilled_counts(gpu):
+    """An engine that spilled owns a u64 count per row of each group (Group::acc) and frees it when it
+    is destroyed.  2^20 reads of 32 nt, then 1000 more with the spill lowered to every 1000 reads: the
+    second add spills, and the length's row counts are 2^20 rows x 8 B = 8 MiB.  Sixteen engines that
+    each leaked them would take 128 MiB of device memory; the free memory may fall by less than half
+    of that (the bound follows from these sizes, not from a measurement)."""
+    import torch
+    import shortseq_amd.batch as B
+    n, extra, engines = 1 << 20, 1000, 16
+    blob, offs, lens = B.synth_ragged_pool_reads(n, 81, 82, 1000, 32, 32, device=gpu)
+    torch.cuda.synchronize(gpu)
+    free0, _total = torch.cuda.mem_get_info(gpu)
+    for _ in range(engines):
+        eng = B.DeviceIngest(gpu)
+        try:
+            eng.set_count_limit(1000)
+            eng.count(blob, offs, lens)
+            eng.count(blob, offs[:extra], lens[:extra])
+            _l, counts, _w = eng.results()
+            assert int(counts.sum()) == n + extra
+        finally:
+            eng.close()
+    free1, _total = torch.cuda.mem_get_info(gpu)
+    drop = free0 - free1
+    print(f"free device memory fell by {drop / 2**20:.1f} MiB over {engines} engines")
+    assert drop < engines * n * 8 // 2
+
+
 @pytest.mark.parametrize("lo,hi", [(0, 40), (33, 100), (100, 300)])
 def test_device_ingest_merge_counts_past_slot(gpu, oracle, lo, hi):
     """Counts a slot cannot take in one merge: with the spill lowered to every 500 reads, a 6-key pool
