@@ -5,7 +5,9 @@ Capacity 2^19 gives 256 regions (rbits 8: a coarse and a fine pass), 2^17 gives 
 pass).  Each case inserts its reads in thirds into one table (global first indices; the later thirds
 meet slices the first wrote), then resets the table and inserts the first third again: the second
 round meets the pending reset (the single-word aggregate writes fresh slices, every other route
-memsets first).  Key input has no Python binding; the drop-in GPU tests cover it.
+memsets first).  Every route gets one uniform pool here; test_counter_route_shapes.py runs the same
+routes, and the two key-input routes (ss_counter_insert_keys through ctypes), on skewed, crafted and
+tile-edge batches.
 """
 import numpy as np
 import pytest
