@@ -60,7 +60,8 @@ def test_all_pairs_gpu(gpu, oracle, L, n, k):
     if total > 4:
         _, p3, total3 = B.hamming_all_pairs(d, L, k, counts=False, max_pairs=3)
         assert total3 == total and p3.shape[0] == 3
-        assert {tuple(int(x) for x in q) for q in p3.cpu().numpy()} <= set(pairs_e)
+        kept = {tuple(int(x) for x in q) for q in p3.cpu().numpy()}
+        assert len(kept) == 3 and kept <= set(pairs_e)
 
 
 @pytest.mark.gpu
@@ -87,7 +88,8 @@ def test_all_pairs_pigeonhole_gpu(gpu, oracle, L, n, k):
     if total > 4:    # truncated pair output: the total still counts every pair, the kept ones are real
         _, p3, total3 = B.hamming_all_pairs(d, L, k, counts=False, max_pairs=3, method="pigeonhole")
         assert total3 == total and p3.shape[0] == 3
-        assert {tuple(int(x) for x in q) for q in p3.cpu().numpy()} <= set(pairs_e)
+        kept = {tuple(int(x) for x in q) for q in p3.cpu().numpy()}
+        assert len(kept) == 3 and kept <= set(pairs_e)
 
 
 def _pair_set(pairs):

@@ -61,7 +61,8 @@ def _check(B, torch, d, L, k, cnt_e, pairs_e, method="bucketed"):
     if total > 4:    # truncated: the total still counts every pair, the kept ones are real
         _, p3, total3 = B.hamming_all_pairs(d, L, k, counts=False, max_pairs=3, method=method)
         assert total3 == total and p3.shape[0] == 3
-        assert {tuple(int(x) for x in q) for q in p3.cpu().numpy()} <= set(pairs_e)
+        kept = {tuple(int(x) for x in q) for q in p3.cpu().numpy()}
+        assert len(kept) == 3 and kept <= set(pairs_e)
 
 
 LONG_CASES = [
@@ -294,6 +295,7 @@ def test_forms_share_the_scratch_back_to_back(gpu, oracle):
             key = pairs_e[:, 0] * n + pairs_e[:, 1]             # sorted: the brute force runs in (i, j) order
             k3 = p3.cpu().numpy().astype(np.int64)
             assert bool(np.isin(k3[:, 0] * n + k3[:, 1], key).all())
+            assert len(np.unique(k3[:, 0] * n + k3[:, 1])) == 3
 
 
 def test_method_table_and_header_constant():

@@ -242,7 +242,8 @@ def _check(B, torch, d, L, k, cnt_e, pairs_e, method):
     if total > 4:    # truncated: the total still counts every pair, the kept ones are real
         _, p3, total3 = B.hamming_all_pairs(d, L, k, counts=False, max_pairs=3, method=method)
         assert total3 == total and p3.shape[0] == 3, method
-        assert {tuple(int(x) for x in q) for q in p3.cpu().numpy()} <= set(pairs_e), method
+        kept = {tuple(int(x) for x in q) for q in p3.cpu().numpy()}
+        assert len(kept) == 3 and kept <= set(pairs_e), method
 
 
 @pytest.mark.gpu
