@@ -545,6 +545,64 @@ int ss_host_trim_adapter3(const uint8_t* h_blob, uint64_t nbytes, const uint64_t
                           uint64_t n, const uint8_t* h_adapter, uint32_t A, uint32_t min_overlap, uint32_t err_div,
                           uint32_t* h_out_lens, uint64_t* h_stats);
 
+/* ------------------------------------------------------------------------------------------------
+ * 3' quality trim of a ragged batch (the -q of cutadapt, fastp and BWA: the step that small-RNA and
+ * amplicon pipelines run before the adapter cut; new in this ABI version, replaces no reference
+ * interface).  As for the adapter no read is moved: d_out_lens[i] is read i's length lowered, and
+ * (d_offsets, d_out_lens) is again the ragged layout of ss_encode_var, ss_trim_adapter3 and
+ * ss_ingest_add_device.  The rule, for a read of length L <= 1024 with Q >= L quality bytes q[0..Q) of
+ * which only q[0..L) are used, a cutoff c in 1..93 and a base b of 33 or 64:
+ *   s = 0; best = 0; stop = L
+ *   for i = L-1 down to 0:
+ *       s += c - (int(q[i]) - b)        (q[i] as an unsigned byte 0..255; the sum fits in 32 bits)
+ *       if s < 0: break
+ *       if s > best: best = s; stop = i
+ *   new length = stop
+ * This is BWA's running-sum rule, which cutadapt's -q uses for the 3' end: ties keep the rightmost
+ * position (the first maximum met wins), s == 0 neither stops the walk nor moves stop, and any byte
+ * value is legal in q (a byte below b is a negative score).  No parity with any tool is claimed or
+ * tested.  Reads with d_lens[i] > SS_MAX_NT (0xFFFFFFFF included) stay as they are and none of their
+ * bytes is read; length 0 stays 0; neither counts in the statistics.
+ * Where the quality bytes are:
+ *   explicit form (d_qoffsets != NULL): read i's qualities are the d_lens[i] bytes at d_qual +
+ *     d_qoffsets[i] (Q == L by contract; '\n' is an ordinary byte).  d_blob is not read.
+ *   FASTQ layout form (d_qoffsets == NULL; d_qual is ignored): d_blob[0..nbytes) is FASTQ text and
+ *     (d_offsets, d_lens) come from ss_fastq_index* over it.  e1 = the first '\n' at a position >=
+ *     d_offsets[i] + L (exactly there on a normal line, further right on one shortened by a NUL), e2 =
+ *     the first '\n' after e1 (the end of the '+' line, which may repeat the header), and the quality
+ *     line is [e2 + 1, e3) with e3 = the next '\n' or nbytes, so Q = e3 - e2 - 1.  A read whose e1 or e2
+ *     does not exist below nbytes, or with Q < L, keeps its length and counts in stats[2]; with Q > L
+ *     the first L bytes are used.  Nothing at or past nbytes is looked at.
+ * The device entry points keep the plain contract (asynchronous on `stream`, no allocation, no
+ * synchronisation, capturable).  d_out_lens may be d_lens itself.  d_stats (nullable): u64[3] = {reads
+ * shortened, bytes removed, reads without a usable quality line}, zeroed by the entry point.  n < 2^32.
+ * Memory is read in whole 16-B aligned chunks, as by ss_trim_adapter3: the blob (layout form) or the
+ * quality bytes (explicit form) must be readable from the start of their first to the end of their last
+ * 16-B chunk (every device allocation is); offsets are trusted.
+ * reads_per_launch (_ex; a test hook): reads per kernel launch, 0 = the library's 2^28 (larger values
+ * are clamped to it); the results do not depend on it.
+ * Kernel (k_trim_quality3): a small group of lanes per read locates the quality line, then walks it from
+ * the right in rounds of one 16-B chunk per lane: chunk totals prefix-summed by shuffles, each lane's 16
+ * bytes walked exactly from its starting sum, the rightmost lane that goes negative ends the read
+ * ("3' quality trim").
+ * SS_EARG (nothing is written): a NULL required pointer with n > 0 (d_offsets, d_lens, d_out_lens;
+ * d_blob in the layout form), d_qoffsets without d_qual, cutoff 0 or above 93, base not 33 or 64,
+ * n >= 2^32.
+ * ss_host_trim_quality3: the same function in plain C++ on host arrays (csrc/host_qtrim.h per read);
+ * qbytes = the size of h_qual (explicit form).  It also validates, before anything is written, that
+ * every read of at most SS_MAX_NT bytes lies inside the blob and, in explicit form, its quality run
+ * inside h_qual[0..qbytes) (SS_EARG).
+ * ---------------------------------------------------------------------------------------------- */
+int ss_trim_quality3(const uint8_t* d_blob, uint64_t nbytes, const uint64_t* d_offsets, const uint32_t* d_lens,
+                     uint64_t n, const uint8_t* d_qual, const uint64_t* d_qoffsets, uint32_t cutoff, uint32_t base,
+                     uint32_t* d_out_lens, uint64_t* d_stats, void* stream);
+int ss_trim_quality3_ex(const uint8_t* d_blob, uint64_t nbytes, const uint64_t* d_offsets, const uint32_t* d_lens,
+                        uint64_t n, const uint8_t* d_qual, const uint64_t* d_qoffsets, uint32_t cutoff, uint32_t base,
+                        uint32_t* d_out_lens, uint64_t* d_stats, uint64_t reads_per_launch, void* stream);
+int ss_host_trim_quality3(const uint8_t* h_blob, uint64_t nbytes, const uint64_t* h_offsets, const uint32_t* h_lens,
+                          uint64_t n, const uint8_t* h_qual, uint64_t qbytes, const uint64_t* h_qoffsets, uint32_t cutoff,
+                          uint32_t base, uint32_t* h_out_lens, uint64_t* h_stats);
+
 /* Multi-GPU counter with region-range ownership: part p of n owns the table regions
  * [ceil(p R / n), ceil((p + 1) R / n)) (R = capacity / slice slots, ss_counter_geometry); the sentinel
  * key ~0 belongs to the owner of its hash region.  Every rank counts its own reads into its own
@@ -634,6 +692,20 @@ int ss_ingest_set_exact(ss_ingest* g, int exact);
  * ss_ingest_reset, like ss_ingest_set_exact.  SS_EARG: A > 64, or A > 0 with a NULL adapter or
  * min_overlap == 0.  With no adapter set no kernel is queued and no buffer is touched. */
 int ss_ingest_set_adapter(ss_ingest* g, const uint8_t* h_adapter, uint32_t A, uint32_t min_overlap, uint32_t err_div);
+/* 3' quality cutoff of the engine (the rule of ss_trim_quality3, FASTQ layout form; new in this ABI
+ * version): every later ss_ingest_add_fastq and _add_fastq_range lowers each chunk's lengths in place
+ * right after its index, on the engine's stream, as part of the index stage and before the adapter trim
+ * if one is set (quality first, then the adapter on the kept prefix: the order every trimmer uses).  A
+ * chunk ends after a newline, not after a record: where its last sequence line has its quality line in
+ * the next bytes of the file (also at the end of a multi-GPU range), the engine reads those one or two
+ * lines from the file and applies csrc/host_qtrim.h to that one read, so the result does not depend on
+ * the chunk size.  Everything after that is unchanged, as for the adapter: a read is judged on its kept
+ * prefix only, a read trimmed to 0 is the empty read, a line of more than 1024 bytes is still the
+ * too-long error, and a record whose quality line is missing or short keeps its length.
+ * ss_ingest_add_blob and ss_ingest_add_device have no quality bytes: the setting does not apply to them.
+ * cutoff 0 clears the setting; it is sticky across ss_ingest_reset.  SS_EARG: cutoff above 93, or a
+ * cutoff with a base other than 33 or 64.  With no cutoff set no kernel is queued and no buffer is touched. */
+int ss_ingest_set_quality(ss_ingest* g, uint32_t cutoff, uint32_t base);
 /* Global read indices of one engine are u64 (a call counts any number of reads); a length's or class's
  * table indexes its rows with a u32 first index, so a group about to pass 2^32 - 1 rows is re-keyed
  * (its distinct keys become its first rows).  Test hook: lower that bound to `rows` (>= 1024) so the

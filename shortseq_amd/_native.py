@@ -102,11 +102,15 @@ SIGNATURES = [
     ("ss_trim_adapter3", C.c_int, [_P, _U64, _P, _P, _U64, _P, _U32, _U32, _U32, _P, _P, _P]),
     ("ss_trim_adapter3_ex", C.c_int, [_P, _U64, _P, _P, _U64, _P, _U32, _U32, _U32, _P, _P, _U64, _P]),
     ("ss_host_trim_adapter3", C.c_int, [_P, _U64, _P, _P, _U64, _P, _U32, _U32, _U32, _P, _P]),
+    ("ss_trim_quality3", C.c_int, [_P, _U64, _P, _P, _U64, _P, _P, _U32, _U32, _P, _P, _P]),
+    ("ss_trim_quality3_ex", C.c_int, [_P, _U64, _P, _P, _U64, _P, _P, _U32, _U32, _P, _P, _U64, _P]),
+    ("ss_host_trim_quality3", C.c_int, [_P, _U64, _P, _P, _U64, _P, _U64, _P, _U32, _U32, _P, _P]),
     ("ss_ingest_create", C.c_int, [C.c_int, C.POINTER(C.c_void_p)]),
     ("ss_ingest_destroy", C.c_int, [_P]),
     ("ss_ingest_reset", C.c_int, [_P]),
     ("ss_ingest_set_exact", C.c_int, [_P, C.c_int]),
     ("ss_ingest_set_adapter", C.c_int, [_P, _P, _U32, _U32, _U32]),
+    ("ss_ingest_set_quality", C.c_int, [_P, _U32, _U32]),
     ("ss_ingest_set_row_limit", C.c_int, [_P, _U64]),
     ("ss_ingest_set_count_limit", C.c_int, [_P, _U64]),
     ("ss_ingest_staging", C.c_int, [_P, _U64, C.POINTER(C.c_void_p)]),
@@ -140,6 +144,7 @@ SIGNATURES = [
 INTERNAL_SIGNATURES = [
     ("ss_counter_last_route", C.c_int, [_P]),
     ("ss_trim_adapter3_shape", C.c_int, [_P, _U64, _P, _P, _U64, _P, _U32, _U32, _U32, _P, _P, _U64, _U32, C.c_int, _P]),
+    ("ss_trim_quality3_shape", C.c_int, [_P, _U64, _P, _P, _U64, _P, _P, _U32, _U32, _P, _P, _U64, _U32, _P]),
 ]
 
 _lib = None

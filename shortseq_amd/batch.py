@@ -31,7 +31,7 @@ __all__ = ["words_for", "wpr_for", "encode", "encode_var", "decode", "decode_var
            "hamming_pair", "encode_hamming_ref", "synth_reads", "synth_pool_reads", "synth_zipf_reads", "zipf_cdf",
            "GpuCounter",
            "raise_read_error", "first_bad_buffer", "fastq_index", "gather_rows", "trim_adapter", "host_trim_adapter",
-           "slice_fixed",
+           "trim_quality", "host_trim_quality", "slice_fixed",
            "slice_var", "hamming_all_pairs", "hamming_nearest", "cluster_pairs", "umi_cluster",
            "GROUPED_ROW_TILE", "hamming_all_pairs_grouped", "umi_cluster_grouped", "HostStager", "host_stager", "encode_host", "decode_host"]
 
@@ -528,6 +528,88 @@ def host_trim_adapter(blob, offsets, lens, adapter, *, min_overlap: int = 3, err
     check(lib().ss_host_trim_adapter3(blob.ctypes.data, blob.size, offsets.ctypes.data, lens.ctypes.data, n, abuf, len(a),
                                       min_overlap, err_div, out.ctypes.data, st.ctypes.data if stats else None),
           "ss_host_trim_adapter3")
+    return (out, st) if stats else out
+
+
+def _quality_args(cutoff: int, base: int) -> None:
+    """The argument checks of ss_trim_quality3 raised as ValueError."""
+    if not 1 <= cutoff <= 93:
+        raise ValueError("quality cutoff in 1 .. 93 expected")
+    if base not in (33, 64):
+        raise ValueError("quality base of 33 or 64 expected")
+
+
+def trim_quality(blob: torch.Tensor, offsets: torch.Tensor, lens: torch.Tensor, cutoff: int, *, base: int = 33,
+                 qual: Optional[torch.Tensor] = None, qoffsets: Optional[torch.Tensor] = None,
+                 out: Optional[torch.Tensor] = None, stats: bool = False, _reads_per_launch: int = 0):
+    """3' quality trim of a ragged batch (one ss_trim_quality3 launch): BWA's running sum from the read's
+    right end, s += cutoff - (q - base) per quality byte, stopped where s < 0; the new length is the
+    rightmost position of the greatest s > 0, or lens[i] (include/shortseq_amd.h, "3' quality trim").
+    With `qual` and `qoffsets` read i's qualities are the lens[i] bytes at qual[qoffsets[i]:]; without
+    them `blob` is FASTQ text, (offsets, lens) its fastq_index, and each read's quality line is found
+    behind its '+' line (a read without a quality line of lens[i] bytes keeps its length).  Reads longer
+    than 1024 keep their length.  No read is moved: (offsets, new lens) feed trim_adapter, encode_var and
+    DeviceIngest.count as they are.  `out` may be `lens` itself.  stats=True also returns an int64 [3]
+    tensor {reads shortened, bytes removed, reads without a usable quality line}."""
+    for t, nm in ((blob, "blob"), (offsets, "offsets"), (lens, "lens")):
+        _require_cuda(t, nm)
+    if offsets.dtype != torch.int64 or lens.dtype not in (torch.int32, torch.uint32) or blob.dtype != torch.uint8:
+        raise TypeError("blob uint8, offsets int64, lens int32 expected")
+    _quality_args(cutoff, base)
+    n = lens.numel()
+    if offsets.numel() != n:
+        raise ValueError("offsets and lens differ in length")
+    if (qual is None) != (qoffsets is None):
+        raise ValueError("qual and qoffsets go together")
+    if qual is not None:
+        _require_cuda(qual, "qual")
+        _require_cuda(qoffsets, "qoffsets")
+        if qual.dtype != torch.uint8 or qoffsets.dtype != torch.int64 or qoffsets.numel() != n:
+            raise TypeError("qual uint8, qoffsets int64 of the reads' count expected")
+    dev = blob.device
+    if out is None:
+        out = torch.empty_like(lens)
+    else:
+        _require_cuda(out, "out")
+        if out.dtype != lens.dtype or out.numel() != n:
+            raise ValueError("out must match lens")
+    st = torch.empty(3, dtype=torch.int64, device=dev) if stats else None
+    check(lib().ss_trim_quality3_ex(blob.data_ptr(), blob.numel(), offsets.data_ptr(), lens.data_ptr(), n, _ptr(qual),
+                                    _ptr(qoffsets), cutoff, base, out.data_ptr(), _ptr(st), _reads_per_launch,
+                                    _stream(dev)), "ss_trim_quality3")
+    return (out, st) if stats else out
+
+
+def host_trim_quality(blob, offsets, lens, cutoff: int, *, base: int = 33, qual=None, qoffsets=None, out=None,
+                      stats: bool = False):
+    """trim_quality on numpy arrays (ss_host_trim_quality3, plain C++): blob and qual uint8, offsets and
+    qoffsets uint64 / int64, lens uint32 / int32.  Also checks that every read of at most 1024 bytes lies
+    inside the blob and, with `qual`, its quality run inside `qual`."""
+    blob = np.ascontiguousarray(blob, dtype=np.uint8)
+    offsets = np.ascontiguousarray(offsets)
+    lens = np.ascontiguousarray(lens)
+    if offsets.dtype not in (np.uint64, np.int64) or lens.dtype not in (np.uint32, np.int32):
+        raise TypeError("blob uint8, offsets uint64, lens uint32 expected")
+    _quality_args(cutoff, base)
+    n = lens.size
+    if offsets.size != n:
+        raise ValueError("offsets and lens differ in length")
+    if (qual is None) != (qoffsets is None):
+        raise ValueError("qual and qoffsets go together")
+    if qual is not None:
+        qual = np.ascontiguousarray(qual, dtype=np.uint8)
+        qoffsets = np.ascontiguousarray(qoffsets)
+        if qoffsets.dtype not in (np.uint64, np.int64) or qoffsets.size != n:
+            raise TypeError("qoffsets uint64 of the reads' count expected")
+    if out is None:
+        out = np.empty_like(lens)
+    elif out.dtype != lens.dtype or out.size != n or not out.flags.c_contiguous:
+        raise ValueError("out must match lens")
+    st = np.zeros(3, dtype=np.uint64) if stats else None
+    check(lib().ss_host_trim_quality3(blob.ctypes.data, blob.size, offsets.ctypes.data, lens.ctypes.data, n,
+                                      None if qual is None else qual.ctypes.data, 0 if qual is None else qual.size,
+                                      None if qual is None else qoffsets.ctypes.data, cutoff, base, out.ctypes.data,
+                                      st.ctypes.data if stats else None), "ss_host_trim_quality3")
     return (out, st) if stats else out
 
 

@@ -19,9 +19,9 @@ CSRC = os.path.join(PKG, "csrc")
 INCLUDE = os.path.join(REPO, "include")
 LIB = os.path.join(PKG, "lib", "libshortseq_amd.so")
 HIP_SOURCES = ["ss_codec.hip", "ss_counter.hip", "ss_fastq.hip", "ss_allpairs.hip", "ss_runtime.hip", "ss_ingest.hip",
-               "ss_stage.hip", "ss_cluster.hip", "ss_nearest.hip", "ss_grouped.hip", "ss_trim.hip"]
+               "ss_stage.hip", "ss_cluster.hip", "ss_nearest.hip", "ss_grouped.hip", "ss_trim.hip", "ss_qtrim.hip"]
 HIP_DEPS = HIP_SOURCES + ["ss_device.h", "ss_hamming.h", "ss_internal.h", "host_codec.h", "fq_reader.h",
-                          "host_threads.h", "host_trim.h", "ss_owned.h"]
+                          "host_threads.h", "host_trim.h", "host_qtrim.h", "ss_owned.h"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = os.environ.get("SHORTSEQ_AMD_ARCH", "gfx950")
 
@@ -58,7 +58,8 @@ def _ext_path(name: str) -> str:
 def build_cython(force: bool = False, verbose: bool = False) -> str:
     pyx = os.path.join(CSRC, "_shortseq.pyx")
     out = _ext_path("_shortseq")
-    deps = [pyx, os.path.join(CSRC, "host_codec.h"), os.path.join(CSRC, "host_trim.h"), os.path.join(INCLUDE, "shortseq_amd.h"), LIB]
+    deps = [pyx, os.path.join(CSRC, "host_codec.h"), os.path.join(CSRC, "host_trim.h"), os.path.join(CSRC, "host_qtrim.h"),
+            os.path.join(INCLUDE, "shortseq_amd.h"), LIB]
     if not os.path.exists(pyx):
         return out
     if force or _stale(out, deps):

@@ -78,6 +78,7 @@ ctypedef int (*f_fastq_split)(const char*, uint32_t, uint64_t*, uint64_t*) noexc
 ctypedef int (*f_add_fastq_range)(ss_ingest*, const char*, uint64_t, uint64_t, uint64_t, uint64_t, uint64_t*) noexcept nogil
 ctypedef int (*f_set_exact)(ss_ingest*, int) noexcept nogil
 ctypedef int (*f_set_adapter)(ss_ingest*, const uint8_t*, uint32_t, uint32_t, uint32_t) noexcept nogil
+ctypedef int (*f_set_quality)(ss_ingest*, uint32_t, uint32_t) noexcept nogil
 ctypedef int (*f_export)(ss_ingest*, uint64_t*) noexcept nogil
 ctypedef int (*f_merge)(ss_ingest*, ss_ingest*, uint64_t) noexcept nogil
 ctypedef int (*f_reserve_merge)(ss_ingest*, ss_ingest**, uint32_t) noexcept nogil
@@ -99,6 +100,7 @@ cdef struct _Abi:
     f_add_fastq_range add_fastq_range
     f_set_exact set_exact
     f_set_adapter set_adapter
+    f_set_quality set_quality
     f_export export_keys
     f_merge merge
     f_reserve_merge reserve_merge
@@ -138,6 +140,7 @@ cdef int _bind_abi() except -1:
     _abi.add_fastq_range = <f_add_fastq_range>_sym(h, b"ss_ingest_add_fastq_range")
     _abi.set_exact = <f_set_exact>_sym(h, b"ss_ingest_set_exact")
     _abi.set_adapter = <f_set_adapter>_sym(h, b"ss_ingest_set_adapter")
+    _abi.set_quality = <f_set_quality>_sym(h, b"ss_ingest_set_quality")
     _abi.export_keys = <f_export>_sym(h, b"ss_ingest_export")
     _abi.merge = <f_merge>_sym(h, b"ss_ingest_merge")
     _abi.reserve_merge = <f_reserve_merge>_sym(h, b"ss_ingest_reserve_merge")
@@ -161,6 +164,9 @@ cdef extern from "host_trim.h":
     bint ssh_trim_prepare "ssh::trim_prepare"(ssh_TrimAdapter* t, const uint8_t* a, uint32_t A, uint32_t min_overlap,
                                               uint32_t err_div) nogil
     uint32_t ssh_trim_read "ssh::trim_read"(const ssh_TrimAdapter& t, const uint8_t* r, uint32_t L) nogil
+
+cdef extern from "host_qtrim.h":
+    uint32_t ssh_qtrim_read "ssh::qtrim_read"(const uint8_t* q, uint32_t L, uint32_t cutoff, uint32_t base) nogil
 
 # Domain constants (short_seq_64.pyx:27-28, short_seq_192.pyx:21-22, short_seq_var.pyx:8-10)
 MIN_64_NT = 0
@@ -978,7 +984,8 @@ cdef bytes _adapter_arg(adapter, min_overlap, err_div):
     return adapter
 
 
-def read_and_count_fastq(filename, device="auto", *, adapter=None, min_overlap=3, err_div=10, _chunk_bytes=0):
+def read_and_count_fastq(filename, device="auto", *, adapter=None, min_overlap=3, err_div=10, quality_cutoff=None,
+                         quality_base=33, _chunk_bytes=0):
     """counter.pyx:57-70 + fast_read.pyx:3-20: keep line 2 of every 4 lines; each kept line loses
     exactly its last character (strlen - 1, short_seq.pyx:50-52); prints the reference's timings.
     device "auto" (the current GPU) / "cuda[:N]" / "all" / a list: the file is cut into one byte
@@ -990,13 +997,26 @@ def read_and_count_fastq(filename, device="auto", *, adapter=None, min_overlap=3
     sequence line is cut at the leftmost position where the adapter matches with an overlap of at
     least min_overlap and at most overlap // err_div mismatches (no indels, not best-scoring;
     include/shortseq_amd.h, "3' adapter trim") before it is counted -- on the device for the GPU paths,
-    with csrc/host_trim.h for "host".  A read is judged on its kept prefix only."""
+    with csrc/host_trim.h for "host".  A read is judged on its kept prefix only.
+    quality_cutoff (1..93; keyword-only, not in the reference) with quality_base (33 or 64): before the
+    adapter cut every sequence line loses its low-quality 3' end by BWA's running-sum rule over the
+    record's quality line (include/shortseq_amd.h, "3' quality trim") -- on the device for the GPU
+    paths, with csrc/host_qtrim.h for "host".  A record whose quality line is missing or shorter than
+    its sequence line keeps its length."""
     import os
     cdef bytes ad = None if adapter is None else _adapter_arg(adapter, min_overlap, err_div)
     cdef ssh_TrimAdapter trim
+    cdef uint32_t qc = 0, qb = 33
+    if quality_cutoff is not None:
+        if not 1 <= quality_cutoff <= 93:
+            raise ValueError("quality_cutoff in 1 .. 93 expected")
+        if quality_base not in (33, 64):
+            raise ValueError("quality_base of 33 or 64 expected")
+        qc = quality_cutoff
+        qb = quality_base
     devs = _resolve_devices(device)
     if devs:
-        return _read_and_count_fastq_gpu(filename, devs, _chunk_bytes, ad, min_overlap, err_div)
+        return _read_and_count_fastq_gpu(filename, devs, _chunk_bytes, ad, min_overlap, err_div, qc, qb)
     if ad is not None:
         ssh_trim_prepare(&trim, <const uint8_t*>PyBytes_AS_STRING(ad), <uint32_t>len(ad), min_overlap, err_div)
     cdef FILE* f
@@ -1005,6 +1025,8 @@ def read_and_count_fastq(filename, device="auto", *, adapter=None, min_overlap=3
     cdef ssize_t got
     cdef size_t count = 1
     cdef size_t ln
+    cdef size_t qn
+    cdef bytes held = None        # with a cutoff: the sequence line that waits for its quality line
     seqs = []
     t1 = time.time()
     fname = filename.encode("utf-8")
@@ -1021,10 +1043,28 @@ def read_and_count_fastq(filename, device="auto", *, adapter=None, min_overlap=3
                 if ln == 0:   # strlen - 1 underflows in the reference -> the too-long error
                     raise Exception(f"Sequences longer than {MAX_VAR_NT} bases are not supported.")
                 ln -= 1
+                if qc:
+                    held = PyBytes_FromStringAndSize(line, ln)
+                else:
+                    if ad is not None and ln <= C_MAX_VAR:
+                        ln = ssh_trim_read(trim, <const uint8_t*>line, <uint32_t>ln)
+                    seqs.append(PyBytes_FromStringAndSize(line, ln))
+            elif held is not None and count % 4 == 0:
+                # the quality line as it stands in the file: every byte up to its newline, NULs included
+                ln = len(held)
+                qn = <size_t>got - (1 if line[got - 1] == b'\n' else 0)
+                if ln <= C_MAX_VAR and qn >= ln:
+                    ln = ssh_qtrim_read(<const uint8_t*>line, <uint32_t>ln, qc, qb)
                 if ad is not None and ln <= C_MAX_VAR:
-                    ln = ssh_trim_read(trim, <const uint8_t*>line, <uint32_t>ln)
-                seqs.append(PyBytes_FromStringAndSize(line, ln))
+                    ln = ssh_trim_read(trim, <const uint8_t*>PyBytes_AS_STRING(held), <uint32_t>ln)
+                seqs.append(held[:ln])
+                held = None
             count += 1
+        if held is not None:      # the file ended before the record's quality line: the read keeps its length
+            ln = len(held)
+            if ad is not None and ln <= C_MAX_VAR:
+                ln = ssh_trim_read(trim, <const uint8_t*>PyBytes_AS_STRING(held), <uint32_t>ln)
+            seqs.append(held[:ln])
     finally:
         fclose(f)
         free(line)
@@ -1046,12 +1086,13 @@ def fastq_stage_times():
 
 
 def _read_and_count_fastq_gpu(filename, devs, uint64_t chunk_bytes=0, bytes adapter=None, uint32_t min_overlap=3,
-                              uint32_t err_div=10):
+                              uint32_t err_div=10, uint32_t quality_cutoff=0, uint32_t quality_base=33):
     """The file streamed through one engine per device: range k of ss_fastq_split on devs[k]
     (parallel preads into pinned staging, chunks ending after a newline, one-read FASTQ index, split
     by length and counted on the device); the ranges reduced on the devices in range order
     (_reduce_fill).  With `adapter` every engine taken trims its chunks' lengths after the index
-    (ss_ingest_set_adapter); the engines are pooled, so the setting is cleared before they go back."""
+    (ss_ingest_set_adapter), and with `quality_cutoff` lowers them before that (ss_ingest_set_quality);
+    the engines are pooled, so both settings are cleared before they go back."""
     import os
     cdef int rc
     cdef Py_ssize_t D = len(devs), k
@@ -1081,6 +1122,8 @@ def _read_and_count_fastq_gpu(filename, devs, uint64_t chunk_bytes=0, bytes adap
             if adapter is not None:
                 _ingest_check(_abi.set_adapter(<ss_ingest*><size_t>g, <const uint8_t*>PyBytes_AS_STRING(adapter),
                                                <uint32_t>len(adapter), min_overlap, err_div), "ingest set adapter")
+            if quality_cutoff:
+                _ingest_check(_abi.set_quality(<ss_ingest*><size_t>g, quality_cutoff, quality_base), "ingest set quality")
             if _abi.fq_stages != NULL:
                 _abi.fq_stages(<ss_ingest*><size_t>g, st_ms, &st_bytes)     # (drop what earlier calls left)
             jobs.append((g, 1, 0, 0, 0, fname, begin[k], begin[k + 1], line0[k], chunk_bytes, None))
@@ -1106,6 +1149,8 @@ def _read_and_count_fastq_gpu(filename, devs, uint64_t chunk_bytes=0, bytes adap
             _engine_nkeys.pop(h, None)
             if adapter is not None:      # (also on an engine that was counted again after SS_EFULL)
                 _abi.set_adapter(<ss_ingest*><size_t>h, NULL, 0, 0, 0)
+            if quality_cutoff:
+                _abi.set_quality(<ss_ingest*><size_t>h, 0, 33)
             _engine_release(d, <ss_ingest*><size_t>h)
     print(f"{t2-t1:.2f}s to read {nseqs} total seqs, and {t3 - t2:.2f}s to count {len(counts)} unique sequences")
     return counts

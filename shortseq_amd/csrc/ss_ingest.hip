@@ -55,6 +55,7 @@
 #include <vector>
 
 #include "fq_reader.h"
+#include "host_qtrim.h"
 #include "ss_internal.h"
 
 namespace {
@@ -804,6 +805,7 @@ struct HostWords {
     ExtractCount extract[kLenBins];     // extract_groups: per group placed
     uint64_t table_size, rekey_count;   // table_size; group_rekey: the entries extracted
     uint64_t fq_counts[3], export_max;  // index_chunk: newlines, records, overflow; ss_ingest_export: the largest count
+    uint32_t seam_len, seam_pad;        // seam_quality: the chunk's last length, there and back
 };
 struct DevWords {                       // the device sides of those that have no buffer of their own
     ExtractCount extract[kLenBins];     // (sized by kLenBins: a group per length bin at the most)
@@ -889,6 +891,9 @@ struct ss_ingest {
     // on the stream before process_chunk sees them (trim_chunk)
     uint8_t adapter[64] = {};
     uint32_t adapter_len = 0, adapter_min_overlap = 0, adapter_err_div = 0;
+    // 3' quality cutoff (ss_ingest_set_quality; 0: none): a FASTQ chunk's lengths are lowered right after
+    // its index, before the adapter trim (seam_quality mends the read whose quality line is not in the chunk)
+    uint32_t qual_cutoff = 0, qual_base = 33;
     DBuf<uint64_t> first_bad;      // [kLenBins + 1]: one u64 per length bin, the class encode's last
     Pinned<HostWords> hw;          // pinned: every small result the device hands back
     Buf<DevWords, DevMem> dw;      // on the device: the count triples, the size query's and the re-key's word
@@ -1910,6 +1915,49 @@ int trim_chunk(ss_ingest* g, const uint8_t* d_buf, uint64_t nbytes, const uint64
                             g->adapter_err_div, d_out, nullptr, g->stream);
 }
 
+// The quality trim of the one read that ss_trim_quality3 could not do on the chunk: a chunk ends after a
+// newline, not after a record, so when `phase` = (lines before the chunk's end) % 4 is 2 or 3 its last
+// sequence line (read nrec - 1) has its quality line in the next bytes of the file, from `pos` on: behind
+// a '+' line (phase 2) or at once (phase 3).  The kernel left that read its length; the rule depends only
+// on that length and the quality bytes, so they are read from the file (in steps: a '+' line may be long)
+// and csrc/host_qtrim.h gives the length, written into the chunk's lengths on the stream.  A '+' line that
+// never ends or a quality line shorter than the read leaves the length as it is, as the kernel does.
+int seam_quality(ss_ingest* g, int fd, uint64_t fsize, uint64_t pos, uint32_t phase, uint64_t nrec) {
+    hipStream_t s = g->stream;
+    uint32_t* seam = &g->hw.p->seam_len;
+    int rc = ss_check(hipMemcpyAsync(seam, g->dlens.p + (nrec - 1), 4, hipMemcpyDeviceToHost, s), "ingest seam length");
+    if (!rc) rc = ss_check(hipStreamSynchronize(s), "ingest seam length");
+    if (rc) return rc;
+    const uint32_t L = *seam;
+    if (L == 0 || L > SS_MAX_NT) return SS_OK;
+    std::vector<uint8_t> buf;
+    uint64_t qstart = 0, scanned = 0;
+    uint32_t skip = phase == 2 ? 1 : 0;          // lines before the quality line
+    while (skip || buf.size() - qstart < L) {
+        while (skip && scanned < buf.size()) {
+            const void* e = memchr(buf.data() + scanned, '\n', buf.size() - scanned);
+            scanned = e ? (uint64_t)((const uint8_t*)e - buf.data()) + 1 : buf.size();
+            if (e) {
+                --skip;
+                qstart = scanned;
+            }
+        }
+        if (!skip && buf.size() - qstart >= L) break;
+        if (pos >= fsize) return SS_OK;          // the file ends first
+        const uint64_t want = std::min<uint64_t>(4096, fsize - pos), old = buf.size();
+        buf.resize(old + want);
+        const uint64_t got = pread_full(fd, buf.data() + old, want, pos);
+        buf.resize(old + got);
+        if (got == 0) return SS_OK;
+        pos += got;
+    }
+    if (memchr(buf.data() + qstart, '\n', L)) return SS_OK;      // a quality line shorter than the read
+    const uint32_t k = ssh::qtrim_read(buf.data() + qstart, L, g->qual_cutoff, g->qual_base);
+    if (k == L) return SS_OK;
+    *seam = k;       // (pinned; the caller waits for the stream before the next chunk can come here)
+    return ss_check(hipMemcpyAsync(g->dlens.p + (nrec - 1), seam, 4, hipMemcpyHostToDevice, s), "ingest seam length");
+}
+
 // the file descriptor of one call, closed however the call ends
 struct Fd {
     const int v;
@@ -2011,6 +2059,14 @@ int ss_ingest_set_adapter(ss_ingest* g, const uint8_t* h_adapter, uint32_t A, ui
     g->adapter_len = A;
     g->adapter_min_overlap = min_overlap;
     g->adapter_err_div = err_div;
+    return SS_OK;
+}
+
+int ss_ingest_set_quality(ss_ingest* g, uint32_t cutoff, uint32_t base) {
+    if (!g) return ss_fail(SS_EARG, "null ingest");
+    if (cutoff && !ssh::qtrim_args_ok(cutoff, base)) return ss_fail(SS_EARG, "ingest: quality cutoff 0 .. 93, base 33 or 64");
+    g->qual_cutoff = cutoff;
+    g->qual_base = cutoff ? base : 33;
     return SS_OK;
 }
 
@@ -2143,6 +2199,7 @@ int ss_ingest_add_fastq_range(ss_ingest* g, const char* path, uint64_t begin, ui
     // right after a newline, so its last line is complete (the strlen - 1 rule of a final line with no
     // newline applies only at the file's end)
     const uint64_t size = std::min<uint64_t>((uint64_t)st.st_size, end);
+    uint64_t fpos = begin;        // where the current chunk starts in the file (the quality seam reads on from its end)
     if (h_nseqs) *h_nseqs = 0;
     if (begin >= size) return SS_OK;
     if (chunk_bytes == 0) chunk_bytes = kFqChunkDefault;
@@ -2171,10 +2228,17 @@ int ss_ingest_add_fastq_range(ss_ingest* g, const char* path, uint64_t begin, ui
         uint64_t nl = 0, nrec = 0;
         rc = ss_check(hipStreamWaitEvent(s, sl.done, 0), "ingest fastq wait");
         if (!rc) rc = index_chunk(g, sl.d.p, c.use, line0, c.at_eof, &nl, &nrec);
-        if (!rc && g->adapter_len && nrec) {     // in place, and waited for: the trim is part of the index stage
-            rc = trim_chunk(g, sl.d.p, c.use, g->offs.p, g->dlens.p, nrec, g->dlens.p);
-            if (!rc) rc = ss_check(hipStreamSynchronize(s), "ingest fq trim");
+        if (!rc && g->qual_cutoff && nrec) {     // quality first, then the adapter on the kept prefix
+            rc = ss_trim_quality3(sl.d.p, c.use, g->offs.p, g->dlens.p, nrec, nullptr, nullptr, g->qual_cutoff, g->qual_base,
+                                  g->dlens.p, nullptr, s);
+            // whether the file goes on is the file's size, not the range's end
+            const uint32_t phase = (uint32_t)((line0 + nl) & 3);
+            if (!rc && (phase == 2 || phase == 3) && fpos + c.use < (uint64_t)st.st_size)
+                rc = seam_quality(g, fd.v, (uint64_t)st.st_size, fpos + c.use, phase, nrec);
         }
+        if (!rc && g->adapter_len && nrec) rc = trim_chunk(g, sl.d.p, c.use, g->offs.p, g->dlens.p, nrec, g->dlens.p);
+        // in place, and waited for: the trims are part of the index stage
+        if (!rc && (g->adapter_len || g->qual_cutoff) && nrec) rc = ss_check(hipStreamSynchronize(s), "ingest fq trim");
         if (rc) break;
         fq.ms[2] += since(ti);
         fq.ms[1] += fq.pieces_ms(k & 1, c.np);     // (all complete: the index synced)
@@ -2184,6 +2248,7 @@ int ss_ingest_add_fastq_range(ss_ingest* g, const char* path, uint64_t begin, ui
         fq.ms[3] += since(tc);
         if (rc) break;
         line0 += nl;
+        fpos += c.use;
         if (c.at_eof || g->bad_index != kNoSlot) break;
         if ((rc = ss_check(hipStreamSynchronize(s), "ingest chunk"))) break;
         rd.release(k);

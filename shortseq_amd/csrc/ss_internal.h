@@ -102,6 +102,12 @@ extern "C" int ss_trim_adapter3_shape(const uint8_t* d_blob, uint64_t nbytes, co
                                       const uint32_t* d_lens, uint64_t n, const uint8_t* h_adapter, uint32_t A,
                                       uint32_t min_overlap, uint32_t err_div, uint32_t* d_out_lens, uint64_t* d_stats,
                                       uint64_t reads_per_launch, uint32_t group, int staged, void* stream);
+// ss_trim_quality3_ex with the lane group open (tools/probe_qtrim.py): group = lanes per read (1, 2, 4, 8
+// or 16; 0 = the library's).  Same results for every group.
+extern "C" int ss_trim_quality3_shape(const uint8_t* d_blob, uint64_t nbytes, const uint64_t* d_offsets,
+                                      const uint32_t* d_lens, uint64_t n, const uint8_t* d_qual,
+                                      const uint64_t* d_qoffsets, uint32_t cutoff, uint32_t base, uint32_t* d_out_lens,
+                                      uint64_t* d_stats, uint64_t reads_per_launch, uint32_t group, void* stream);
 // One length class of the drop-in engine's chunk for ss_classes_verify_fold: its table (set_words(W1)),
 // its m packed rows of W1 words, and the table's first row index for them.
 struct ss_class_rows {
